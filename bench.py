@@ -11,7 +11,10 @@ per-GPU batch fixed, global batch 32*N.
 Contract: ``python bench.py --gpus N --steps K --warmup W`` (N>1 under
 ``torch.distributed.run``); W untimed warmup steps (rounded up to whole
 epochs), then EXACTLY K timed steps bracketed by barrier + synchronize, the
-MAX elapsed over ranks, one JSON line from rank 0.
+MAX elapsed over ranks, one JSON line from rank 0. Such a plain run does only
+that: set up, warm up, time the K steps, print the line. ``--full`` adds the
+side measurements below (comparator, toy-MLP figures); ``--dump-outputs DIR``
+writes what the last timed step left (parameters, losses) as ``DIR/<name>.npy``.
 
 Every timed step does the full work: batch gather by sampler index, forward,
 loss, backward, all-reduce of the gradient bucket across all ranks, SGD update.
@@ -29,13 +32,15 @@ from the launch-to-launch list cache (the driver's 20 timed steps at positions
   reference stock PyTorch-ROCm loop (torch DDP, DataLoader + DistributedSampler,
             nn.Linear, F.cross_entropy, torch.optim.SGD) -- the comparator
 
-Comparator: after the headline, the SAME process times the stock PyTorch-ROCm
+Comparator (``--full``): after the headline, the SAME process times the stock PyTorch-ROCm
 reference loop (``--engine reference`` body: torch DDP over RCCL, DataLoader +
 DistributedSampler, same model/batch/N) and reports ``ref_samples_per_s`` and
 ``speedup_vs_torch``; ``vs_baseline`` is that same-node ratio ("the
 like-for-like comparator is the unmodified reference scripts running on
 PyTorch-ROCm on the same node"), the survey's CPU/gloo probe ratio is kept as
-``vs_cpu_probe``.
+``vs_cpu_probe``. Also under ``--full`` only: the toy-MLP side measurements
+(``mlp_*`` / ``mlp_bf16_*`` keys, ``_mlp_side``). Without ``--full`` those keys are
+absent and ``vs_baseline`` is null.
 
 Fallback: if the requested engine fails on ANY rank (no GPU, no peer memory for
 the in-kernel xGMI exchange, an xGMI poll timeout, a hipGraph capture error, a
@@ -104,12 +109,19 @@ def parse(argv=None):
     ap.add_argument("--stamps", action="store_true",
                     help="persistent engine: diagnostic run with in-kernel phase timers (separate from the timed run)")
     ap.add_argument("--out", default=None, help="also append the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the side measurements: the toy-MLP figures (mlp_*, "
+                         "mlp_bf16_*) and the same-process stock PyTorch-ROCm comparator (ref_*, vs_baseline); "
+                         "off by default, so a plain run does only what its headline figure needs")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path left in its last step (params, "
+                         "losses) as DIR/<name>.npy (float32); same arguments give the same inputs")
     ap.add_argument("--no_mlp_side", action="store_true",
-                    help="skip the extra toy-MLP measurement (mlp_us_per_step) after the headline run")
+                    help="with --full: skip the extra toy-MLP measurement (mlp_us_per_step) after the headline run")
     ap.add_argument("--deadline", type=float, default=float(os.environ.get("PTDT_BENCH_DEADLINE", 420)),
                     help="whole-run deadline in seconds (0: none); on expiry an error JSON line is printed")
     ap.add_argument("--no_ref", action="store_true",
-                    help="skip the same-process stock PyTorch-ROCm comparator after the headline")
+                    help="with --full: skip the same-process stock PyTorch-ROCm comparator after the headline")
     ap.add_argument("--ref_steps", type=int, default=None,
                     help="timed steps of the comparator (default max(--steps, 256); its warmup max(--warmup, 32))")
     ap.add_argument("--no_fallback", action="store_true",
@@ -243,7 +255,8 @@ def run_fused(args, rank, world, dev, comm, dec, graph=True, allreduce=None):
     t = _timed(comm, dev, lambda: [run(n) for n in timed])
     if xg is not None:
         xg.check()
-    extra = {"replicas_in_sync": _replicas_in_sync(comm, eng.P),
+    extra = {"_outputs": _outputs(args, params=eng.P, losses=losses),
+             "replicas_in_sync": _replicas_in_sync(comm, eng.P),
              "steps_per_epoch": S, "steps_per_graph": full if graph else None, "warmup_steps_run": warm_steps,
              "final_loss": float(losses[(args.steps - 1) % S].item()),
              "allreduce": "xgmi-oneshot (in-kernel)" if xg is not None else "rccl",
@@ -343,6 +356,8 @@ def run_persistent(args, rank, world, dev, comm, dec):
         t = _timed(comm, dev, timed_steps)
     dec.check("xgmi_poll_timed", not _xgmi_error(xg), "an in-kernel xGMI poll timed out (a peer never arrived)")
     in_sync = _replicas_in_sync(comm, eng.P)
+    # the parameters after the K-th timed step and the losses of the last timed launch's steps
+    outs = _outputs(args, params=eng.P, losses=losses[:launches[-1]] if launches else losses[:0])
     phase = None
     if args.stamps:  # diagnostic pass AFTER the timed region (timers cost a little)
         st = torch.zeros(32, dtype=torch.int64, device=dev)
@@ -384,7 +399,8 @@ def run_persistent(args, rank, world, dev, comm, dec):
             phase["helper_per_step"] = {n: round(v[23 + k] / args.steps, 1) for k, n in enumerate(
                 ("other", "barrier1_wait", "barrier2_wait", "produce", "stage_write", "stage_sel_issue", "loss_flush"))}
     last = (args.steps - 1) % chunk
-    extra = {"replicas_in_sync": in_sync, "steps_per_epoch": S, "launches_timed": math.ceil(args.steps / chunk),
+    extra = {"_outputs": outs, "replicas_in_sync": in_sync, "steps_per_epoch": S,
+             "launches_timed": math.ceil(args.steps / chunk),
              "sampler": ("torch.randperm-identical DistributedSampler order (torch_perm kernel in the timed region)"
                          if args.sampler == "torch" else
                          "device Feistel permutation: DistributedSampler semantics (per-epoch reshuffle, padded "
@@ -400,7 +416,7 @@ def run_persistent(args, rank, world, dev, comm, dec):
                          "workgroup; sampler shard recomputed in-kernel each epoch")}
     if phase:
         extra["phase_timers"] = phase
-    if args.model == "linear" and not args.no_mlp_side:
+    if args.full and args.model == "linear" and not args.no_mlp_side:
         extra.update(_mlp_side(args, rank, world, dev, comm, xg, "fp32", dec))
         extra.update(_mlp_side(args, rank, world, dev, comm, xg, "bf16", dec))
     return t, extra
@@ -478,8 +494,10 @@ def run_autograd(args, rank, world, dev, comm, dec):
         return l
 
     steps(max(args.warmup, 1))
-    t = _timed(comm, dev, lambda: steps(args.steps))
-    return t, {"kernels": "native DDP reducer + native linear/CE/SGD, eager"}
+    last = {}
+    t = _timed(comm, dev, lambda: last.update(loss=steps(args.steps)))
+    outs = _outputs(args, params=_flat_params(model), losses=last["loss"].detach().reshape(1))
+    return t, {"_outputs": outs, "kernels": "native DDP reducer + native linear/CE/SGD, eager"}
 
 
 # --------------------------------------------------------------------------- reference
@@ -531,10 +549,47 @@ def run_reference(args, rank, world, dev, comm, dec=None, steps=None, warmup=Non
                 l = F.cross_entropy(ddp(xs), ys)
             l.backward()
             opt.step()
+        state["loss"] = l
 
     run(max(warmup, 1))
     t = _timed(comm, dev, lambda: run(steps), label=label)
-    return t, {"kernels": "stock torch: DataLoader+DistributedSampler, nn.Linear, F.cross_entropy, torch DDP, SGD"}
+    outs = _outputs(args, params=_flat_params(model), losses=state["loss"].detach().reshape(1))
+    return t, {"_outputs": outs,
+               "kernels": "stock torch: DataLoader+DistributedSampler, nn.Linear, F.cross_entropy, torch DDP, SGD"}
+
+
+# --------------------------------------------------------------------------- outputs
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def _flat_params(model) -> torch.Tensor:
+    return torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+
+
+def _outputs(args, **tensors):
+    """Host copies (taken right after the timed region, before any side measurement) of what the
+    timed path left for its caller; None unless --dump-outputs is given."""
+    if not args.dump_outputs:
+        return None
+    return {k: v.detach().to("cpu", copy=True) for k, v in tensors.items()}
+
+
+def _dump_outputs(path, outs) -> dict:
+    """Write each array as ``path/<name>.npy`` (float32, float64 kept); an array over its share of
+    DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its elements. Returns name -> shape."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(outs), 1)
+    shapes = {}
+    for name, t in outs.items():
+        a = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+        if a.nbytes > share:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 # --------------------------------------------------------------------------- timing
@@ -672,8 +727,8 @@ def _record(args, world, value, elapsed, extra):
                    "engine": getattr(args, "engine_used", args.engine)},
         "baseline_note": "vs_baseline = value / ref_samples_per_s: the stock PyTorch-ROCm reference loop (torch DDP "
                          "over RCCL, DataLoader+DistributedSampler, same model/batch/N) timed in this same process "
-                         "after the headline; vs_cpu_probe divides by BASELINE.md's CPU/gloo survey probe; the "
-                         "reference publishes no GPU DDP number",
+                         "after the headline when --full is given (null otherwise); vs_cpu_probe divides by "
+                         "BASELINE.md's CPU/gloo survey probe; the reference publishes no GPU DDP number",
         **extra,
     }
     return rec
@@ -781,13 +836,14 @@ def main(argv=None):
         dl.cancel()
         sys.exit(4)
     args.engine_used = used
+    outs = extra.pop("_outputs", None)
     extra["engine_path"] = used
     if failures:
         extra["fallback"] = failures
     value = args.steps * args.batch_size * world / elapsed
     extra["timing"] = dict(_TIMINGS)
     done["rec"] = _record(args, world, value, elapsed, extra)
-    if not (args.no_ref or args.share_gpu or used == "reference"):
+    if args.full and not (args.no_ref or args.share_gpu or used == "reference"):
         dl.set_phase("comparator (stock PyTorch-ROCm reference loop)")
         cmp, why = {}, None
         try:
@@ -800,6 +856,9 @@ def main(argv=None):
         else:
             extra.update(cmp)
             extra["speedup_vs_torch"] = round(value / extra["ref_samples_per_s"], 3)
+    if outs is not None and rank == 0:
+        dl.set_phase("dump outputs")
+        extra["dumped_outputs"] = _dump_outputs(args.dump_outputs, outs)
     dl.set_phase("report")
     extra["timing"] = dict(_TIMINGS)
     extra["gpu_warmup_ms_before_timed"] = _GPU_WARM_MS if dev.type == "cuda" else 0.0

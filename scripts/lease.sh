@@ -67,7 +67,7 @@ for s in "$@"; do
     tests)     tstep pytest_gpu 1000 python3 -u -m pytest -q -rf --timeout 120 --timeout-method thread tests -m gpu ;;
     tests:*)   tstep pytest_sel 600 python3 -u -m pytest -q -rf --timeout 120 --timeout-method thread ${s#tests:} ;;
     smoke)     step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    driver)    for i in 1 2 3; do jstep bench_driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5; done ;;
+    driver)    for i in 1 2 3; do jstep bench_driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full; done ;;
     rehab)     # A/B of the warm-up split (PTDT_BENCH_REHEARSALS), interleaved, headline only
                for i in 1 2 3; do for r in 1 2 3; do
                  jstep rehab 120 env PTDT_BENCH_REHEARSALS=$r python3 bench.py --steps 20 --warmup 5 --no_ref --no_mlp_side
@@ -81,7 +81,7 @@ for s in "$@"; do
                  jstep pinab 120 python3 bench.py --steps 20 --warmup 5 --no_ref --no_mlp_side
                  jstep pinab 120 env PTDT_BENCH_PIN_CU=0 python3 bench.py --steps 20 --warmup 5 --no_ref --no_mlp_side
                done ;;
-    default)   jstep bench_default 300 python3 bench.py ;;
+    default)   jstep bench_default 300 python3 bench.py --full ;;
     tp20k)     # toy-MLP TP engine, bf16 and fp32, long launch
                for dt in bf16 fp32; do jstep tp20k 300 python3 bench.py --model mlp --dtype $dt --steps 20000 --warmup 2000 --no_ref; done ;;
     hl20k)     # headline engine alone, long launch: per-step cost without the fixed part
@@ -184,7 +184,7 @@ for s in "$@"; do
                rm -rf "$O/prof_${T}_memtrace" ;;  # ~200k dispatches (MIOpen find): too big to copy back
     mlpstamps) jstep mlpstamps 300 python3 bench.py --model mlp --steps 20000 --warmup 2000 --stamps --no_ref ;;
     profdrv)   prof drvonly 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no_ref --no_mlp_side ;;
-    prof)      prof driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5
+    prof)      prof driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full
                prof reference 300 python3 bench.py --engine reference --steps 200 --warmup 20 ;;
     tppmcab)   # TP engine PMC per step: this tree vs tools/bin/_C_r4.so (round-4 build), two passes each
                for side in cur r4; do
@@ -257,8 +257,8 @@ for s in "$@"; do
                done ;;
     sideab)    # driver command incl. the toy-MLP side measurement: this tree vs tools/bin/_C_base.so
                for r in 1 2 3 4; do
-                 jstep sideab_cur 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no_ref
-                 jstep sideab_base 300 env PTDT_EXT_PATH=$PWD/tools/bin/_C_base.so python3 bench.py --gpus 1 --steps 20 --warmup 5 --no_ref
+                 jstep sideab_cur 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no_ref
+                 jstep sideab_base 300 env PTDT_EXT_PATH=$PWD/tools/bin/_C_base.so python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no_ref
                done ;;
     pmc_tp)    pmc tp1 "$P1" python3 bench.py --model mlp --persist tp --steps 20000 --warmup 1 --no_mlp_side
                pmc tp2 "$P2" python3 bench.py --model mlp --persist tp --steps 20000 --warmup 1 --no_mlp_side ;;
