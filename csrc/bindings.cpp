@@ -5,8 +5,6 @@
 // before launching (a bad launch on MI355X can reset the whole node) and
 // launches on the caller's current HIP stream, so all of them are capturable
 // into hipGraphs via torch.cuda.graph.
-#include <time.h>
-
 #include <map>
 #include <mutex>
 #include <utility>
@@ -95,8 +93,10 @@ void fused_mlp_step_py(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor>
   TORCH_CHECK(X.scalar_type() == at::kFloat && P.scalar_type() == at::kFloat && G.scalar_type() == at::kFloat,
               "fused_mlp_step: fp32 dataset/params/grads");
   TORCH_CHECK(X.dim() == 2 && X.size(1) == Din, "fused_mlp_step: X must be [N, Din]");
-  const int64_t Dh = H > 0 ? H : Din;
-  const int64_t np = (H > 0 ? H * Din + (has_bias ? H : 0) : 0) + Dout * Dh + (has_bias ? Dout : 0);
+  FusedMlpArgs a{};
+  a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout;
+  a.has_bias = has_bias ? 1 : 0;
+  const int64_t np = fused_mlp_num_params(a);
   TORCH_CHECK(P.numel() == np && G.numel() == np, "fused_mlp_step: flat param/grad size mismatch (want ",
               np, ")");
   TORCH_CHECK(loss_out.is_cuda() && loss_out.scalar_type() == at::kFloat && loss_out.numel() >= 1);
@@ -120,7 +120,6 @@ void fused_mlp_step_py(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor>
   TORCH_CHECK(fused_mlp_lds_bytes((int)B, (int)Din, (int)H, (int)Dout) <= 160 * 1024,
               "fused_mlp_step: model/batch too large for one workgroup's LDS; use the layered path");
   c10::hip::HIPGuard guard(X.device().index());
-  FusedMlpArgs a{};
   a.X = X.data_ptr<float>();
   a.Yf = ptr_or_null<const float>(Yf);
   a.Yi = ptr_or_null<const int64_t>(Yi);
@@ -130,10 +129,8 @@ void fused_mlp_step_py(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor>
   a.mom = ptr_or_null<float>(mom);
   a.opt_step = ptr_or_null<int32_t>(opt_step);
   a.loss_out = loss_out.data_ptr<float>();
-  a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout;
   a.loss_kind = (int)loss_kind;
   a.ignore_index = (int)ignore_index;
-  a.has_bias = has_bias ? 1 : 0;
   a.grad_scale = (float)grad_scale;
   a.accumulate = accumulate ? 1 : 0;
   a.update_mode = (int)update_mode;
@@ -151,152 +148,27 @@ void fused_mlp_step_py(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor>
   hip_check(ptdt::fused_mlp_step(a, cur_stream(X)), "fused_mlp_step");
 }
 
-// Validated persistent-launch arguments (shared by the one-shot call and
-// PersistentPlan). Throws on any shape/dtype/sharding mismatch: a bad launch
-// of a resident kernel can reset the node.
-struct PersistBuild {
-  FusedMlpArgs a{};
-  PersistArgs pa{};
-};
-
-PersistBuild build_persistent(const Tensor& X, const c10::optional<Tensor>& Yf, const c10::optional<Tensor>& Yi,
-                              const Tensor& P, const Tensor& G, const c10::optional<Tensor>& mom,
-                              const c10::optional<Tensor>& opt_step, int64_t B, int64_t Din, int64_t H, int64_t Dout,
-                              int64_t loss_kind, int64_t ignore_index, bool has_bias, double lr, double momentum,
-                              double dampening, double weight_decay, bool nesterov,
-                              const std::shared_ptr<XgmiComm>& ar, int64_t n_steps, int64_t W, int64_t rank,
-                              int64_t num_samples, bool shuffle, int64_t seed, const Tensor& cursor,
-                              const Tensor& losses, const c10::optional<Tensor>& stamps, int64_t variant,
-                              bool x_zero_padded, const c10::optional<Tensor>& idx, int64_t cursor_j,
-                              const c10::optional<Tensor>& lcache = c10::nullopt, int64_t idx_e0 = 0) {
-  TORCH_CHECK(X.is_cuda(), "X must be a GPU tensor");  // rows may be padded: checked below
-  check_gpu(P, "P");
-  check_gpu(G, "G");
-  TORCH_CHECK(X.scalar_type() == at::kFloat && P.scalar_type() == at::kFloat && G.scalar_type() == at::kFloat);
-  TORCH_CHECK(X.dim() == 2 && X.size(1) == Din && X.stride(1) == 1 && X.stride(0) >= Din,
-              "persistent: X must be [N, Din] with unit column stride (rows may be padded)");
-  const int64_t N = X.size(0);
-  const int64_t Dh = H > 0 ? H : Din;
-  const int64_t np = (H > 0 ? H * Din + (has_bias ? H : 0) : 0) + Dout * Dh + (has_bias ? Dout : 0);
-  TORCH_CHECK(P.numel() == np && G.numel() == np, "persistent: flat param/grad size mismatch");
-  TORCH_CHECK(cursor.is_cuda() && cursor.scalar_type() == at::kInt && cursor.numel() == 2, "cursor: int32[2] GPU");
-  TORCH_CHECK(losses.is_cuda() && losses.scalar_type() == at::kFloat && losses.numel() >= n_steps, "losses: f32[n]");
-  TORCH_CHECK(num_samples > 0 && num_samples * W >= N && W > 0 && rank >= 0 && rank < W, "persistent: bad sampler");
-  if (loss_kind == kLossCEIndex) {
-    TORCH_CHECK(Yi.has_value() && Yi->defined() && Yi->scalar_type() == at::kLong && Yi->numel() == N);
-  } else {
-    TORCH_CHECK(Yf.has_value() && Yf->defined() && Yf->scalar_type() == at::kFloat && Yf->numel() == N * Dout);
+// Query-format name of a selected engine: "wave:L<lanes per row>R<rows per lane group>K<features
+// per lane>", "tp:<n>waves", "tp_bf16:<n>waves", "workgroup:mfma" or "workgroup".
+std::string engine_name(const PersistChoice& c) {
+  switch (c.engine) {
+    case kEngWave: return "wave:L" + std::to_string(c.L) + "R" + std::to_string(c.R) + "K" + std::to_string(c.kp);
+    case kEngTp: return "tp:" + std::to_string(c.waves) + "waves";
+    case kEngTpBf16: return "tp_bf16:" + std::to_string(c.waves) + "waves";
+    case kEngWorkgroupMfma: return "workgroup:mfma";
+    case kEngWorkgroup: return "workgroup";
+    // the query has always named a workgroup engine for configurations the plan refuses
+    default: return c.refused == kEngWorkgroupMfma ? "workgroup:mfma" : "workgroup";
   }
-  if (mom.has_value() && mom->defined()) TORCH_CHECK(mom->numel() == np && mom->is_cuda());
-  const int world = ar ? ar->world() : 1;
-  TORCH_CHECK(world == W, "persistent: all-reduce world != sampler world");
-  PersistBuild b;
-  FusedMlpArgs& a = b.a;
-  a.X = X.data_ptr<float>();
-  a.Yf = ptr_or_null<const float>(Yf);
-  a.Yi = ptr_or_null<const int64_t>(Yi);
-  a.P = P.data_ptr<float>();
-  a.G = G.data_ptr<float>();
-  a.mom = ptr_or_null<float>(mom);
-  a.opt_step = ptr_or_null<int32_t>(opt_step);
-  a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout;
-  a.ldx = (int)X.stride(0);
-  a.x_padded = x_zero_padded ? 1 : 0;
-  a.loss_kind = (int)loss_kind;
-  a.ignore_index = (int)ignore_index;
-  a.has_bias = has_bias ? 1 : 0;
-  a.grad_scale = 1.f;
-  a.update_mode = 2;
-  a.lr = (float)lr; a.momentum = (float)momentum; a.dampening = (float)dampening;
-  a.weight_decay = (float)weight_decay; a.nesterov = nesterov ? 1 : 0;
-  if (ar && ar->world() > 1) {
-    TORCH_CHECK(ar->ready(), "persistent: xGMI communicator not opened");
-    TORCH_CHECK(np <= ar->max_elems(), "persistent: bucket larger than the xGMI buffer");
-    TORCH_CHECK(ar->rank() == rank, "persistent: rank mismatch");
-    a.ar = ar->args();
-  } else {
-    a.ar.world = 1;
-  }
-  PersistArgs& pa = b.pa;
-  pa.n_steps = (int)n_steps;
-  pa.N = (int)N;
-  pa.W = (int)W;
-  pa.rank = (int)rank;
-  pa.num_samples = (int)num_samples;
-  pa.shuffle = shuffle ? 1 : 0;
-  pa.seed = (uint64_t)seed;
-  pa.cursor = cursor.data_ptr<int32_t>();
-  pa.losses = losses.data_ptr<float>();
-  if (stamps.has_value() && stamps->defined()) {
-    TORCH_CHECK(stamps->is_cuda() && stamps->scalar_type() == at::kLong && stamps->numel() >= 9, "stamps: int64[9]");
-    pa.stamps = stamps->data_ptr<int64_t>();
-    pa.stamps_n = (int)stamps->numel();
-  }
-  pa.variant = (int)variant;
-  pa.cursor_host_pos = -1;
-  if (idx.has_value() && idx->defined()) {
-    // [num_samples] (one epoch: cursor_j is the step in it) or [E, num_samples]
-    // (epochs idx_e0..idx_e0+E-1: cursor_j is the absolute position epoch * S + step)
-    TORCH_CHECK(idx->is_cuda() && idx->scalar_type() == at::kInt && idx->is_contiguous() &&
-                    idx->size(-1) == num_samples && idx->dim() <= 2 && idx->device() == X.device(),
-                "persistent: idx must be a contiguous int32 GPU tensor [E,] num_samples on X's device");
-    const int64_t S = (num_samples + B - 1) / B;
-    pa.idx = idx->data_ptr<int32_t>();
-    pa.idx_epochs = idx->dim() == 2 ? (int)idx->size(0) : 1;
-    pa.idx_e0 = idx->dim() == 2 ? (int)idx_e0 : 0;
-    TORCH_CHECK(cursor_j >= (int64_t)pa.idx_e0 * S && cursor_j + n_steps <= (int64_t)(pa.idx_e0 + pa.idx_epochs) * S,
-                "persistent: with explicit index lists a launch must stay inside the provided epochs");
-    pa.cursor_host_pos = cursor_j;
-  }
-  if (lcache.has_value() && lcache->defined()) {  // [2][al4(num_samples)] lists + [2] epoch tags
-    const int64_t stride = (num_samples + 3) & ~int64_t(3);
-    TORCH_CHECK(lcache->is_cuda() && lcache->scalar_type() == at::kInt && lcache->is_contiguous() &&
-                    lcache->numel() == 2 * stride + 2 && lcache->device() == X.device(),
-                "persistent: list cache must be int32[2 * al4(num_samples) + 2] on X's device");
-    pa.lcache = lcache->data_ptr<int32_t>();
-    pa.ltag = pa.lcache + 2 * stride;
-  }
-  const bool wave = variant != kPersistWorkgroup && variant != kPersistMfma && variant != kPersistTp &&
-                    variant != kPersistTpBf16 && linear_wave_supported(a, pa);
-  const bool tp = !wave && (variant == kPersistAuto || variant == kPersistTp || variant == kPersistTpBf16) && H > 0 &&
-                  mlp_tp_supported(a, pa);
-  const bool mfma = !wave && !tp && mlp_mfma_persistent_supported(a, pa);
-  TORCH_CHECK(wave || mfma || tp || (variant < kPersistWave),
-              "persistent: the requested engine variant does not support this configuration");
-  TORCH_CHECK(wave || tp || fused_mlp_persistent_lds_bytes((int)B, (int)Din, (int)H, (int)Dout, (int)num_samples,
-                                                           world) <= 160 * 1024,
-              "persistent: model + epoch index list do not fit one workgroup's LDS");
-  return b;
-}
-
-void fused_mlp_persistent_py(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor> Yi, Tensor P, Tensor G,
-                             c10::optional<Tensor> mom, c10::optional<Tensor> opt_step, int64_t B, int64_t Din,
-                             int64_t H, int64_t Dout, int64_t loss_kind, int64_t ignore_index, bool has_bias,
-                             double lr, double momentum, double dampening, double weight_decay, bool nesterov,
-                             std::shared_ptr<XgmiComm> ar, int64_t n_steps, int64_t W, int64_t rank,
-                             int64_t num_samples, bool shuffle, int64_t seed, Tensor cursor, Tensor losses,
-                             c10::optional<Tensor> stamps, int64_t variant, bool x_zero_padded,
-                             c10::optional<Tensor> idx, int64_t cursor_j) {
-  const PersistBuild b = build_persistent(X, Yf, Yi, P, G, mom, opt_step, B, Din, H, Dout, loss_kind, ignore_index,
-                                          has_bias, lr, momentum, dampening, weight_decay, nesterov, ar, n_steps, W,
-                                          rank, num_samples, shuffle, seed, cursor, losses, stamps, variant,
-                                          x_zero_padded, idx, cursor_j);
-  c10::hip::HIPGuard guard(X.device().index());
-  hip_check(fused_mlp_persistent(b.a, b.pa, cur_stream(X)), "fused_mlp_persistent");
 }
 
 // A persistent engine launch planned once: arguments validated, engine and
 // kernel chosen, LDS attribute set, tensors kept alive. launch(n) is a bare
 // hipLaunchKernel on the caller's current stream -- the short-run fixed cost
 // (bench --steps 20, one launch per Trainer.train) is the kernel, not the host.
-int64_t mono_ns() {
-  timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
-}
-
 class PersistentPlan {
  public:
+  // Throws on any shape/dtype/sharding mismatch: a bad launch of a resident kernel can reset the node.
   PersistentPlan(Tensor X, c10::optional<Tensor> Yf, c10::optional<Tensor> Yi, Tensor P, Tensor G,
                  c10::optional<Tensor> mom, c10::optional<Tensor> opt_step, int64_t B, int64_t Din, int64_t H,
                  int64_t Dout, int64_t loss_kind, int64_t ignore_index, bool has_bias, double lr, double momentum,
@@ -307,15 +179,98 @@ class PersistentPlan {
       : keep_{X, P, G, cursor, losses}, ar_(ar), capacity_(losses.numel()), dev_(X.device().index()) {
     for (const auto* t : {&Yf, &Yi, &mom, &opt_step, &stamps, &idx, &lcache})
       if (t->has_value() && (*t)->defined()) keep_.push_back(**t);
-    const bool has_idx = idx.has_value() && idx->defined();
     steps_per_epoch_ = (num_samples + B - 1) / B;
-    const int64_t first = has_idx && idx->dim() == 2 ? idx_e0 * steps_per_epoch_ : 0;
-    const PersistBuild b = build_persistent(X, Yf, Yi, P, G, mom, opt_step, B, Din, H, Dout, loss_kind, ignore_index,
-                                            has_bias, lr, momentum, dampening, weight_decay, nesterov, ar, 1, W, rank,
-                                            num_samples, shuffle, seed, cursor, losses, stamps, variant,
-                                            x_zero_padded, idx, has_idx ? first : -1, lcache, idx_e0);
+    TORCH_CHECK(X.is_cuda(), "X must be a GPU tensor");  // rows may be padded: checked below
+    check_gpu(P, "P");
+    check_gpu(G, "G");
+    TORCH_CHECK(X.scalar_type() == at::kFloat && P.scalar_type() == at::kFloat && G.scalar_type() == at::kFloat);
+    TORCH_CHECK(X.dim() == 2 && X.size(1) == Din && X.stride(1) == 1 && X.stride(0) >= Din,
+                "persistent: X must be [N, Din] with unit column stride (rows may be padded)");
+    const int64_t N = X.size(0);
+    FusedMlpArgs& a = L_.a;
+    a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout;
+    a.has_bias = has_bias ? 1 : 0;
+    const int64_t np = fused_mlp_num_params(a);
+    TORCH_CHECK(P.numel() == np && G.numel() == np, "persistent: flat param/grad size mismatch");
+    TORCH_CHECK(cursor.is_cuda() && cursor.scalar_type() == at::kInt && cursor.numel() == 2, "cursor: int32[2] GPU");
+    TORCH_CHECK(losses.is_cuda() && losses.scalar_type() == at::kFloat && losses.numel() >= 1, "losses: f32[n]");
+    TORCH_CHECK(num_samples > 0 && num_samples * W >= N && W > 0 && rank >= 0 && rank < W, "persistent: bad sampler");
+    if (loss_kind == kLossCEIndex) {
+      TORCH_CHECK(Yi.has_value() && Yi->defined() && Yi->scalar_type() == at::kLong && Yi->numel() == N);
+    } else {
+      TORCH_CHECK(Yf.has_value() && Yf->defined() && Yf->scalar_type() == at::kFloat && Yf->numel() == N * Dout);
+    }
+    if (mom.has_value() && mom->defined()) TORCH_CHECK(mom->numel() == np && mom->is_cuda());
+    TORCH_CHECK((ar ? ar->world() : 1) == W, "persistent: all-reduce world != sampler world");
+    a.X = X.data_ptr<float>();
+    a.Yf = ptr_or_null<const float>(Yf);
+    a.Yi = ptr_or_null<const int64_t>(Yi);
+    a.P = P.data_ptr<float>();
+    a.G = G.data_ptr<float>();
+    a.mom = ptr_or_null<float>(mom);
+    a.opt_step = ptr_or_null<int32_t>(opt_step);
+    a.ldx = (int)X.stride(0);
+    a.x_padded = x_zero_padded ? 1 : 0;
+    a.loss_kind = (int)loss_kind;
+    a.ignore_index = (int)ignore_index;
+    a.grad_scale = 1.f;
+    a.update_mode = 2;
+    a.lr = (float)lr; a.momentum = (float)momentum; a.dampening = (float)dampening;
+    a.weight_decay = (float)weight_decay; a.nesterov = nesterov ? 1 : 0;
+    if (ar && ar->world() > 1) {
+      TORCH_CHECK(ar->ready(), "persistent: xGMI communicator not opened");
+      TORCH_CHECK(np <= ar->max_elems(), "persistent: bucket larger than the xGMI buffer");
+      TORCH_CHECK(ar->rank() == rank, "persistent: rank mismatch");
+      a.ar = ar->args();
+    } else {
+      a.ar.world = 1;
+    }
+    PersistArgs& pa = L_.p;
+    pa.n_steps = 1;
+    pa.N = (int)N;
+    pa.W = (int)W;
+    pa.rank = (int)rank;
+    pa.num_samples = (int)num_samples;
+    pa.shuffle = shuffle ? 1 : 0;
+    pa.seed = (uint64_t)seed;
+    pa.cursor = cursor.data_ptr<int32_t>();
+    pa.losses = losses.data_ptr<float>();
+    if (stamps.has_value() && stamps->defined()) {
+      TORCH_CHECK(stamps->is_cuda() && stamps->scalar_type() == at::kLong && stamps->numel() >= 9, "stamps: int64[9]");
+      pa.stamps = stamps->data_ptr<int64_t>();
+      pa.stamps_n = (int)stamps->numel();
+    }
+    pa.variant = (int)variant;
+    pa.cursor_host_pos = -1;
+    if (idx.has_value() && idx->defined()) {
+      // [num_samples] (one epoch: positions are steps in it) or [E, num_samples]
+      // (epochs idx_e0..idx_e0+E-1: positions are absolute, epoch * S + step)
+      TORCH_CHECK(idx->is_cuda() && idx->scalar_type() == at::kInt && idx->is_contiguous() &&
+                      idx->size(-1) == num_samples && idx->dim() <= 2 && idx->device() == X.device(),
+                  "persistent: idx must be a contiguous int32 GPU tensor [E,] num_samples on X's device");
+      pa.idx = idx->data_ptr<int32_t>();
+      pa.idx_epochs = idx->dim() == 2 ? (int)idx->size(0) : 1;
+      pa.idx_e0 = idx->dim() == 2 ? (int)idx_e0 : 0;
+      pa.cursor_host_pos = (int64_t)pa.idx_e0 * steps_per_epoch_;
+      TORCH_CHECK(persist_span_ok(L_, pa.cursor_host_pos, 1),
+                  "persistent: with explicit index lists a launch must stay inside the provided epochs");
+    }
+    if (lcache.has_value() && lcache->defined()) {  // [2][al4(num_samples)] lists + [2] epoch tags
+      const int64_t stride = (num_samples + 3) & ~int64_t(3);
+      TORCH_CHECK(lcache->is_cuda() && lcache->scalar_type() == at::kInt && lcache->is_contiguous() &&
+                      lcache->numel() == 2 * stride + 2 && lcache->device() == X.device(),
+                  "persistent: list cache must be int32[2 * al4(num_samples) + 2] on X's device");
+      pa.lcache = lcache->data_ptr<int32_t>();
+      pa.ltag = pa.lcache + 2 * stride;
+    }
     c10::hip::HIPGuard guard(dev_);
-    hip_check(fused_mlp_persistent_prepare(b.a, b.pa, &L_), "persistent plan");
+    const hipError_t e = fused_mlp_persistent_prepare(&L_);
+    const PersistChoice& c = L_.choice;
+    TORCH_CHECK(c.engine != kEngNone || c.refused != kEngNone,
+                "persistent: the requested engine variant does not support this configuration");
+    TORCH_CHECK(c.engine != kEngNone, "persistent: model + epoch index list do not fit one workgroup's LDS");
+    hip_check(e, "persistent plan");
+    engine_ = engine_name(c);
   }
   // n steps from the device cursor; with explicit index lists, cursor_pos is
   // the host's view of the cursor (epoch * steps_per_epoch + step; one-epoch
@@ -323,9 +278,7 @@ class PersistentPlan {
   void launch(int64_t n, int64_t cursor_pos) { launch_impl(n, cursor_pos, -1, 0); }
   void launch_impl(int64_t n, int64_t cursor_pos, int start_e, int start_j) {
     TORCH_CHECK(n >= 0 && n <= capacity_, "persistent plan: n_steps exceeds the losses buffer");
-    const int64_t S = steps_per_epoch_;
-    TORCH_CHECK(L_.p.idx == nullptr || (cursor_pos >= (int64_t)L_.p.idx_e0 * S &&
-                                        cursor_pos + n <= (int64_t)(L_.p.idx_e0 + L_.p.idx_epochs) * S),
+    TORCH_CHECK(persist_span_ok(L_, cursor_pos, (int)n),
                 "persistent plan: with explicit index lists a launch must stay inside the provided epochs");
     c10::hip::HIPGuard guard(dev_);
     hip_check(persistent_launch(L_, (int)n, L_.p.idx ? cursor_pos : -1, c10::hip::getCurrentHIPStream(dev_).stream(),
@@ -342,6 +295,8 @@ class PersistentPlan {
     launch_impl(n, pos, (int)(pos / S), (int)(pos % S));
   }
   int64_t capacity() const { return capacity_; }
+  // query-format name (persistent_engine) of the engine this plan prepared
+  const std::string& engine() const { return engine_; }
   ~PersistentPlan() {
     if (ev_) hipEventDestroy(ev_);
   }
@@ -364,11 +319,7 @@ class PersistentPlan {
     if (ev_ == nullptr) hip_check(hipEventCreate(&ev_), "hipEventCreate");
     const int64_t t0 = mono_ns();
     if (mode == 3 || mode == 5) {
-      L_.p.n_steps = (int)n;
-      L_.p.cursor_host_pos = -1;
-      L_.p.has_start = 1;
-      L_.p.start_e = (int)(pos / S);
-      L_.p.start_j = (int)(pos % S);
+      persist_set_position(L_, (int)n, -1, (int)(pos / S), (int)(pos % S));
       void* args[] = {&L_.a, &L_.p};
       hip_check(hipExtLaunchKernel(L_.fn, dim3(1), dim3(L_.threads), args, L_.lds, st, nullptr, ev_, 0),
                 "hipExtLaunchKernel");
@@ -406,6 +357,7 @@ class PersistentPlan {
   int dev_;
   int64_t steps_per_epoch_ = 0;
   PersistLaunch L_;
+  std::string engine_;
   hipEvent_t ev_ = nullptr;  // timeline probe (launch_wait_at)
 };
 
@@ -461,31 +413,21 @@ std::vector<std::vector<int64_t>> clock_calibrate_py(int64_t n) {
   return {a, b, c};
 }
 
-// Which persistent engine fused_mlp_persistent would run for this configuration
-// ("workgroup", or "wave:L<lanes per row>R<rows per lane group>K<features per lane>").
-std::string persistent_engine(int64_t B, int64_t Din, int64_t H, int64_t Dout, int64_t loss_kind, int64_t num_samples,
-                              int64_t world, int64_t variant, bool has_bias) {
+// Which persistent engine a plan would run for this configuration, before there is a dataset tensor:
+// any row stride (the caller zero-pads X rows to the layout's x_width when needed) and num_samples rows.
+PersistChoice persistent_choice(int64_t B, int64_t Din, int64_t H, int64_t Dout, int64_t loss_kind, int64_t num_samples,
+                                int64_t world, int64_t variant, bool has_bias) {
   FusedMlpArgs a{};
   a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout; a.loss_kind = (int)loss_kind;
   a.has_bias = has_bias ? 1 : 0;
   a.ar.world = (int)world;
-  a.ldx = kWaveLdxAny;  // the caller zero-pads X rows to the layout's width when needed
+  a.ldx = kWaveLdxAny;
   a.x_padded = 1;
   PersistArgs pa{};
   pa.num_samples = (int)num_samples;
   pa.variant = (int)variant;
   pa.N = (int)std::max<int64_t>(num_samples, 1);
-  if (variant != kPersistWorkgroup && variant != kPersistMfma && variant != kPersistTp && variant != kPersistTpBf16 &&
-      linear_wave_supported(a, pa)) {
-    int L = 0, R = 0, kp = 0;
-    linear_wave_layout(a, pa, &L, &R, &kp);
-    return "wave:L" + std::to_string(L) + "R" + std::to_string(R) + "K" + std::to_string(kp);
-  }
-  if (variant == kPersistTpBf16 && H > 0 && mlp_tp_supported(a, pa)) return "tp_bf16:" + std::to_string(H / 16) + "waves";
-  if ((variant == kPersistAuto || variant == kPersistTp) && H > 0 && mlp_tp_supported(a, pa))
-    return "tp:" + std::to_string(H / 16) + "waves";
-  if (variant != kPersistWorkgroup && mlp_mfma_persistent_supported(a, pa)) return "workgroup:mfma";
-  return "workgroup";
+  return persistent_select(a, pa);
 }
 
 // ------------------------------------------------------------- torch-identical sampler orders
@@ -1583,14 +1525,6 @@ PYBIND11_MODULE(_C, m) {
         py::arg("has_bias"), py::arg("grad_scale"), py::arg("accumulate"), py::arg("update_mode"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"),
         py::arg("ar") = nullptr);
-  m.def("fused_mlp_persistent", &fused_mlp_persistent_py, py::arg("X"), py::arg("Yf"), py::arg("Yi"), py::arg("P"),
-        py::arg("G"), py::arg("mom"), py::arg("opt_step"), py::arg("B"), py::arg("Din"), py::arg("H"),
-        py::arg("Dout"), py::arg("loss_kind"), py::arg("ignore_index"), py::arg("has_bias"), py::arg("lr"),
-        py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"), py::arg("ar"),
-        py::arg("n_steps"), py::arg("W"), py::arg("rank"), py::arg("num_samples"), py::arg("shuffle"),
-        py::arg("seed"), py::arg("cursor"), py::arg("losses"), py::arg("stamps") = py::none(),
-        py::arg("variant") = 0, py::arg("x_zero_padded") = false, py::arg("idx") = py::none(),
-        py::arg("cursor_j") = -1);
   py::class_<PersistentPlan, std::shared_ptr<PersistentPlan>>(m, "PersistentPlan")
       .def(py::init<Tensor, c10::optional<Tensor>, c10::optional<Tensor>, Tensor, Tensor, c10::optional<Tensor>,
                     c10::optional<Tensor>, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, bool, double, double,
@@ -1607,6 +1541,7 @@ PYBIND11_MODULE(_C, m) {
       .def("launch", &PersistentPlan::launch, py::arg("n_steps"), py::arg("cursor_pos") = -1)
       .def("launch_at", &PersistentPlan::launch_at, py::arg("n_steps"), py::arg("pos"))
       .def_property_readonly("capacity", &PersistentPlan::capacity)
+      .def_property_readonly("engine", &PersistentPlan::engine)
       .def("set_timeline", &PersistentPlan::set_timeline, py::arg("addr"))
       .def("last_launch_ns", &PersistentPlan::last_launch_ns)
       .def("launch_wait_at", &PersistentPlan::launch_wait_at, py::arg("n_steps"), py::arg("pos"), py::arg("mode"),
@@ -1628,9 +1563,20 @@ PYBIND11_MODULE(_C, m) {
     hip_check(hipStreamSynchronize(c10::hip::getCurrentHIPStream((int)dev).stream()), "hipStreamSynchronize");
     return mono_ns();
   });
-  m.def("persistent_engine", &persistent_engine, py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"),
+  py::class_<PersistChoice>(m, "PersistChoice")
+      .def_property_readonly("name", &engine_name)
+      .def_readonly("x_width", &PersistChoice::x_width);
+  m.def("persistent_choice", &persistent_choice, py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"),
         py::arg("loss_kind"), py::arg("num_samples"), py::arg("world"), py::arg("variant") = 0,
         py::arg("has_bias") = true);
+  m.def(
+      "persistent_engine",
+      [](int64_t B, int64_t Din, int64_t H, int64_t Dout, int64_t loss_kind, int64_t num_samples, int64_t world,
+         int64_t variant, bool has_bias) {
+        return engine_name(persistent_choice(B, Din, H, Dout, loss_kind, num_samples, world, variant, has_bias));
+      },
+      py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"), py::arg("loss_kind"), py::arg("num_samples"),
+      py::arg("world"), py::arg("variant") = 0, py::arg("has_bias") = true);
   m.def("fused_mlp_lds_bytes", [](int B, int Din, int H, int Dout) { return fused_mlp_lds_bytes(B, Din, H, Dout); });
   m.def("sgd_flat_", &sgd_flat_);
   m.def("adam_flat_", &adam_flat_);

@@ -31,7 +31,6 @@
 
 #include "common.h"
 #include "kernels.h"
-#include <time.h>
 #include "sampler.h"
 
 namespace ptdt {
@@ -952,24 +951,6 @@ const void* pick_persist_mfma(int loss, int H) {
   }
 }
 
-bool mfma_engine(const FusedMlpArgs& a, const PersistArgs& p) {
-  return a.H > 0 && (p.variant == kPersistAuto || p.variant == kPersistMfma) &&
-         mlp_mfma_shape_ok(a.B, a.Din, a.H, a.Dout) && !(p.variant == kPersistAuto && mlp_tp_supported(a, p));
-}
-
-hipError_t check_dims(const FusedMlpArgs& a) {
-  if (a.B <= 0 || a.Din <= 0 || a.Dout <= 0 || a.H < 0) return hipErrorInvalidValue;
-  const int64_t widest = a.Din > a.H ? (a.Din > a.Dout ? a.Din : a.Dout) : (a.H > a.Dout ? a.H : a.Dout);
-  if ((int64_t)a.B * widest >= (1ll << 30)) return hipErrorInvalidValue;
-  return hipSuccess;
-}
-
-int64_t num_params(const FusedMlpArgs& a) {
-  const int Dh = a.H > 0 ? a.H : a.Din;
-  return (a.H > 0 ? (int64_t)a.H * a.Din + (a.has_bias ? a.H : 0) : 0) + (int64_t)a.Dout * Dh +
-         (a.has_bias ? a.Dout : 0);
-}
-
 }  // namespace
 
 size_t fused_mlp_lds_bytes(int B, int Din, int H, int Dout) {
@@ -993,13 +974,20 @@ size_t fused_mlp_persistent_lds_bytes(int B, int Din, int H, int Dout, int num_s
   return (size_t)fl * sizeof(float);
 }
 
+hipError_t fused_mlp_check_dims(const FusedMlpArgs& a) {
+  if (a.B <= 0 || a.Din <= 0 || a.Dout <= 0 || a.H < 0) return hipErrorInvalidValue;
+  const int64_t widest = a.Din > a.H ? (a.Din > a.Dout ? a.Din : a.Dout) : (a.H > a.Dout ? a.H : a.Dout);
+  if ((int64_t)a.B * widest >= (1ll << 30)) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+
 hipError_t fused_mlp_step(const FusedMlpArgs& a, hipStream_t s) {
-  PTDT_HIP_CHECK(check_dims(a));
+  PTDT_HIP_CHECK(fused_mlp_check_dims(a));
   const size_t lds = fused_mlp_lds_bytes(a.B, a.Din, a.H, a.Dout);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   int mode = a.update_mode == 1 ? kPre : kNone;
   if (a.ar.world > 0) {
-    if (num_params(a) > a.ar.max_elems || a.update_mode == 1 || a.accumulate) return hipErrorInvalidValue;
+    if (fused_mlp_num_params(a) > a.ar.max_elems || a.update_mode == 1 || a.accumulate) return hipErrorInvalidValue;
     mode = a.update_mode == 2 ? kArPost : kArOnly;
   }
   const void* fn = a.H > 0 ? pick_loss<true>(a.loss_kind, mode) : pick_loss<false>(a.loss_kind, mode);
@@ -1010,67 +998,16 @@ hipError_t fused_mlp_step(const FusedMlpArgs& a, hipStream_t s) {
   return hipLaunchKernel(fn, dim3(1), dim3(threads), args, lds, s);
 }
 
-hipError_t fused_mlp_persistent_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out) {
-  PTDT_HIP_CHECK(check_dims(a));
-  if (a.update_mode != 2 || a.accumulate || p.cursor == nullptr || p.losses == nullptr || p.num_samples <= 0 ||
-      p.N <= 0 || p.W <= 0 || p.rank < 0 || p.rank >= p.W)
-    return hipErrorInvalidValue;
-  if (a.ar.world > 1 && (num_params(a) > a.ar.max_elems || a.ar.world != p.W || a.ar.rank != p.rank))
-    return hipErrorInvalidValue;
-  if (p.variant != kPersistWorkgroup && p.variant != kPersistMfma && p.variant != kPersistTp &&
-      p.variant != kPersistTpBf16 && linear_wave_supported(a, p))
-    return linear_wave_prepare(a, p, out);
-  if ((p.variant == kPersistAuto || p.variant == kPersistTp || p.variant == kPersistTpBf16) && a.H > 0 &&
-      mlp_tp_supported(a, p))
-    return mlp_tp_prepare(a, p, out);
-  if (p.variant >= kPersistWave && p.variant != kPersistMfma) return hipErrorInvalidValue;
-  const size_t lds = fused_mlp_persistent_lds_bytes(a.B, a.Din, a.H, a.Dout, p.num_samples, a.ar.world);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const bool mf = mfma_engine(a, p);
-  if (p.variant == kPersistMfma && !mf) return hipErrorInvalidValue;
+bool mlp_mfma_supported(const FusedMlpArgs& a) { return a.H > 0 && mlp_mfma_shape_ok(a.B, a.Din, a.H, a.Dout); }
+
+// the workgroup engine's half of fused_mlp_persistent_prepare (persist_plan.hip)
+hipError_t fused_mlp_workgroup_prepare(PersistLaunch* L) {
+  const FusedMlpArgs& a = L->a;
+  const bool mf = L->choice.engine == kEngWorkgroupMfma;
   const void* fn = mf ? pick_persist_mfma(a.loss_kind, a.H)
                       : (a.H > 0 ? pick_persist<true>(a.loss_kind) : pick_persist<false>(a.loss_kind));
-  if (lds > 64 * 1024)
-    PTDT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  out->fn = fn;
-  out->threads = mf ? kMfThreads : (a.H > 0 ? 1024 : 256);
-  out->lds = lds;
-  out->a = a;
-  out->p = p;
-  return hipSuccess;
+  return persist_set_kernel(L, fn, mf ? kMfThreads : (a.H > 0 ? 1024 : 256),
+                            fused_mlp_persistent_lds_bytes(a.B, a.Din, a.H, a.Dout, L->p.num_samples, a.ar.world));
 }
-
-hipError_t persistent_launch(PersistLaunch& L, int n_steps, int64_t cursor_host_pos, hipStream_t s, int start_e,
-                             int start_j) {
-  if (n_steps <= 0) return hipSuccess;
-  if (L.fn == nullptr) return hipErrorInvalidValue;
-  if (L.p.idx != nullptr) {  // explicit lists cover epochs [idx_e0, idx_e0 + idx_epochs) only
-    const int64_t S = (L.p.num_samples + L.a.B - 1) / L.a.B;
-    if (cursor_host_pos < (int64_t)L.p.idx_e0 * S || cursor_host_pos + n_steps > (int64_t)(L.p.idx_e0 + L.p.idx_epochs) * S)
-      return hipErrorInvalidValue;
-  }
-  L.p.n_steps = n_steps;
-  L.p.cursor_host_pos = cursor_host_pos;
-  L.p.has_start = start_e >= 0 ? 1 : 0;
-  L.p.start_e = start_e;
-  L.p.start_j = start_j;
-  void* args[] = {&L.a, &L.p};
-  timespec t0, t1;
-  clock_gettime(CLOCK_MONOTONIC, &t0);
-  const hipError_t e = hipLaunchKernel(L.fn, dim3(1), dim3(L.threads), args, L.lds, s);
-  clock_gettime(CLOCK_MONOTONIC, &t1);
-  L.host_ns[0] = (int64_t)t0.tv_sec * 1000000000 + t0.tv_nsec;
-  L.host_ns[1] = (int64_t)t1.tv_sec * 1000000000 + t1.tv_nsec;
-  return e;
-}
-
-hipError_t fused_mlp_persistent(const FusedMlpArgs& a, const PersistArgs& p, hipStream_t s) {
-  if (p.n_steps <= 0) return check_dims(a);
-  PersistLaunch L;
-  PTDT_HIP_CHECK(fused_mlp_persistent_prepare(a, p, &L));
-  return persistent_launch(L, p.n_steps, p.cursor_host_pos, s);
-}
-
-bool mlp_mfma_persistent_supported(const FusedMlpArgs& a, const PersistArgs& p) { return mfma_engine(a, p); }
 
 }  // namespace ptdt

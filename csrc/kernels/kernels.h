@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <time.h>
 
 #include "../comm/xgmi.h"
 
@@ -56,6 +57,12 @@ struct FusedMlpArgs {
   XgmiArgs ar;           // in-kernel one-shot all-reduce (ar.world == 0: off; needs update_mode 2 or 0)
 };
 hipError_t fused_mlp_step(const FusedMlpArgs& a, hipStream_t s);
+// elements of the flat parameter / gradient / momentum buffers
+inline int64_t fused_mlp_num_params(const FusedMlpArgs& a) {
+  const int Dh = a.H > 0 ? a.H : a.Din;
+  return (a.H > 0 ? (int64_t)a.H * a.Din + (a.has_bias ? a.H : 0) : 0) + (int64_t)a.Dout * Dh +
+         (a.has_bias ? a.Dout : 0);
+}
 
 // Persistent DDP step engine: ONE launch runs `n_steps` full DDP steps of the
 // same model with parameters, momentum and the epoch's sampler indices kept
@@ -93,12 +100,12 @@ struct PersistArgs {
   // [3] after the final parameter / cursor stores. May point at host-mapped memory.
   int64_t* tl;
 };
-// Engine choice: the register-resident single-wave engine (linear_wave.hip) runs
-// Linear(Din, Dout) models with B <= 64 and small Dout; everything else runs the
-// LDS workgroup engine (fused_mlp.hip). kPersistAuto picks the wave engine when
-// it supports the configuration.
-// kPersistWaveRows / kPersistWaveF restrict the wave engine to one lane-layout
-// family (row groups across DPP rows / feature groups across DPP rows).
+// Engine variants. WHICH engine a (variant, shape) pair runs is decided in one place,
+// persistent_select() (persist_plan.hip); the notes here only say what each variant names.
+// kPersistWave: the register-resident single-wave engine (linear_wave.hip) for Linear(Din, Dout)
+// models with B <= 64 and small Dout; kPersistWaveRows / kPersistWaveF restrict it to one
+// lane-layout family (row groups across DPP rows / feature groups across DPP rows).
+// kPersistWorkgroup: the LDS workgroup engine (fused_mlp.hip), any Linear[-ReLU-Linear].
 #ifndef PTDT_WAVE_PREFETCH
 #define PTDT_WAVE_PREFETCH 3
 #endif
@@ -112,15 +119,13 @@ __host__ __device__ __forceinline__ int wave_list_stride(int num_samples, int B)
   return (((num_samples + B - 1) / B) * B + 64 + 3) & ~3;
 }
 // kPersistMfma: the workgroup engine with the 4-wave MFMA step body for
-// Linear-ReLU-Linear (B <= 32, Din <= 32, H in 16..64 step 16, Dout <= 16);
-// kPersistAuto picks it for those shapes.
+// Linear-ReLU-Linear (B <= 32, Din <= 32, H in 16..64 step 16, Dout <= 16).
 // kPersistTp: Linear-ReLU-Linear tensor-parallel across the waves of one
 // workgroup (mlp_tp.hip: each wave owns 16 hidden units, every product on
-// MFMA, one barrier per step); kPersistAuto picks it for B <= 32, Din <= 32,
-// H in 16..64 step 16, Dout <= 16.
+// MFMA, one barrier per step), same shape limits with Din + bias <= 32.
 // kPersistTpBf16: the same engine on bf16 operands (torch.autocast(bfloat16) rounding points,
-// fp32 master weights and SGD; v_mfma_f32_16x16x32_bf16 / 16x16x16_bf16). Never picked by
-// kPersistAuto: bf16 is requested explicitly (FusedMLPStep(dtype="bf16"), bench --dtype bf16).
+// fp32 master weights and SGD; v_mfma_f32_16x16x32_bf16 / 16x16x16_bf16); bf16 is requested
+// explicitly (FusedMLPStep(dtype="bf16"), bench --dtype bf16).
 enum PersistVariant : int {
   kPersistAuto = 0, kPersistWorkgroup = 1, kPersistWave = 2, kPersistWaveRows = 3, kPersistWaveF = 4,
   kPersistMfma = 5, kPersistTp = 6, kPersistTpBf16 = 7
@@ -132,7 +137,22 @@ __device__ __forceinline__ const int32_t* given_list(const PersistArgs& p, int e
   k = k < 0 ? 0 : (k >= p.idx_epochs ? p.idx_epochs - 1 : k);
   return p.idx + (int64_t)k * p.num_samples;
 }
-hipError_t fused_mlp_persistent(const FusedMlpArgs& a, const PersistArgs& p, hipStream_t s);
+// The engine a configuration runs, as persistent_select() resolved it.
+enum PersistEngine : int { kEngNone, kEngWave, kEngTp, kEngTpBf16, kEngWorkgroupMfma, kEngWorkgroup };
+struct PersistChoice {
+  PersistEngine engine = kEngNone;
+  int L = 0, R = 0, kp = 0;  // wave layout (engine == kEngWave): L lanes per row, R rows per lane group, kp
+                             // features per lane
+  int waves = 0;             // tp engines: H / 16
+  int x_width = 0;           // row width the wave engine reads (lanes * kp; 0 otherwise)
+  PersistEngine refused = kEngNone;  // engine == kEngNone: the workgroup engine the variant rules reached but
+                                     // whose LDS exceeds 160 KiB (kEngNone: the forced variant does not support
+                                     // the configuration)
+};
+// The variant rules, nowhere else: auto tries wave, then tp, then workgroup:mfma, then workgroup;
+// a forced variant names one engine (tp_bf16 only ever forced) and gives kEngNone when that engine
+// does not support the configuration; a workgroup engine past the LDS bound gives kEngNone.
+PersistChoice persistent_select(const FusedMlpArgs& a, const PersistArgs& p);
 // A persistent launch resolved once (engine choice, kernel, LDS size, argument
 // checks): relaunching it only sets n_steps (and the explicit-list cursor) and
 // calls hipLaunchKernel, so a short run pays no per-call planning.
@@ -142,6 +162,7 @@ struct PersistLaunch {
   size_t lds = 0;
   FusedMlpArgs a{};
   PersistArgs p{};
+  PersistChoice choice{};       // what fused_mlp_persistent_prepare selected
   int64_t host_ns[2] = {0, 0};  // CLOCK_MONOTONIC right before / after the last hipLaunchKernel
 };
 // Timeline probe support (timeline.hip): thread 0 of wave 0 writes the realtime counter.
@@ -153,17 +174,41 @@ __device__ __forceinline__ void tl_mark(int64_t* tl, int k) {
 // with its realtime counter in out[k]; host-mapped buffers. Returns per ping
 // (host ns before the flag store, host ns when the answer was seen, device ticks).
 hipError_t clock_calibrate(int n, int64_t* host_set, int64_t* host_seen, int64_t* dev_ticks);
-hipError_t fused_mlp_persistent_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out);
+inline int64_t mono_ns() {  // CLOCK_MONOTONIC
+  timespec t;
+  clock_gettime(CLOCK_MONOTONIC, &t);
+  return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
+}
+// The plan path (persist_plan.hip). The caller fills L->a and L->p; prepare selects the engine
+// (L->choice, set even when it refuses) and resolves kernel, threads and LDS bytes.
+hipError_t fused_mlp_persistent_prepare(PersistLaunch* L);
 hipError_t persistent_launch(PersistLaunch& L, int n_steps, int64_t cursor_host_pos, hipStream_t s,
                              int start_e = -1, int start_j = 0);
-bool linear_wave_supported(const FusedMlpArgs& a, const PersistArgs& p);
-bool mlp_mfma_persistent_supported(const FusedMlpArgs& a, const PersistArgs& p);
+// explicit index lists cover epochs [idx_e0, idx_e0 + idx_epochs) only: n steps from pos stay inside them
+inline bool persist_span_ok(const PersistLaunch& L, int64_t pos, int n) {
+  if (L.p.idx == nullptr) return true;
+  const int64_t S = (L.p.num_samples + L.a.B - 1) / L.a.B;
+  return pos >= (int64_t)L.p.idx_e0 * S && pos + n <= (int64_t)(L.p.idx_e0 + L.p.idx_epochs) * S;
+}
+// what changes from launch to launch: the step count and where the cursor stands (start_e < 0: the
+// kernel loads the device cursor)
+inline void persist_set_position(PersistLaunch& L, int n, int64_t cursor_pos, int start_e, int start_j) {
+  L.p.n_steps = n;
+  L.p.cursor_host_pos = cursor_pos;
+  L.p.has_start = start_e >= 0 ? 1 : 0;
+  L.p.start_e = start_e;
+  L.p.start_j = start_j;
+}
+// shared tail of the per-engine prepares: the >64 KiB dynamic-LDS opt-in, then kernel, threads, LDS bytes
+hipError_t persist_set_kernel(PersistLaunch* L, const void* fn, int threads, size_t lds);
+// per-engine halves of selection and prepare; persist_plan.hip is their only caller
+bool linear_wave_choose(const FusedMlpArgs& a, const PersistArgs& p, PersistChoice* c);
 bool mlp_tp_supported(const FusedMlpArgs& a, const PersistArgs& p);
-hipError_t mlp_tp_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out);
-// lane layout the wave engine picks: L lanes per row, R rows per lane group, kp features per lane
-void linear_wave_layout(const FusedMlpArgs& a, const PersistArgs& p, int* L, int* R, int* kp);
-hipError_t linear_wave_persistent(const FusedMlpArgs& a, const PersistArgs& p, hipStream_t s);
-hipError_t linear_wave_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out);
+bool mlp_mfma_supported(const FusedMlpArgs& a);
+hipError_t fused_mlp_check_dims(const FusedMlpArgs& a);
+hipError_t linear_wave_prepare(PersistLaunch* L);
+hipError_t mlp_tp_prepare(PersistLaunch* L);
+hipError_t fused_mlp_workgroup_prepare(PersistLaunch* L);
 size_t fused_mlp_persistent_lds_bytes(int B, int Din, int H, int Dout, int num_samples, int world);
 // LDS bytes the step needs (host check against the 160 KiB per-CU budget).
 size_t fused_mlp_lds_bytes(int B, int Din, int H, int Dout);

@@ -59,16 +59,14 @@ double model_cycles(int L, int R, int kp, int dout) {
   return fwd + loss + bwd + sgd + fetch;
 }
 
-struct Choice {
-  const void* fn = nullptr;
-  int L = 0, R = 0, kp = 0;
-};
+}  // namespace
 
-Choice choose(const FusedMlpArgs& a, const PersistArgs& p) {
-  Choice best;
-  if (a.H != 0 || a.B <= 0 || a.B > 64 || a.Dout <= 0) return best;
-  if (a.ar.world > kXgmiMaxRanks) return best;
-  if (a.B <= 0 || lds_bytes(a, p) + kStaticLds > 160 * 1024) return best;
+// The layout search: fills c (engine kEngWave, layout, x_width) with the cheapest supported lane
+// layout and returns true, or leaves c alone and returns false when the wave engine cannot run this.
+bool linear_wave_choose(const FusedMlpArgs& a, const PersistArgs& p, PersistChoice* c) {
+  if (a.H != 0 || a.B <= 0 || a.B > 64 || a.Dout <= 0) return false;
+  if (a.ar.world > kXgmiMaxRanks) return false;
+  if (a.B <= 0 || lds_bytes(a, p) + kStaticLds > 160 * 1024) return false;
   const bool ar = a.ar.world > 1;
   static const int kLR[][2] = {{1, 1}, {2, 1}, {4, 1}, {8, 1}, {2, 2}, {4, 2}, {0, 1}, {0, 2}, {0, 4}};
   double best_cost = 1e30;
@@ -94,52 +92,30 @@ Choice choose(const FusedMlpArgs& a, const PersistArgs& p) {
     if (L == 0 && ((int64_t)p.N * row * 4 >= (1ll << 31) || p.N >= (1 << 24) || row * 4 >= (1 << 24) ||
                    (int64_t)p.N * 8 >= (1ll << 31) || (int64_t)p.N * a.Dout * 4 >= (1ll << 31)))
       continue;
-    const void* fn = pick(a.loss_kind, ar, L, R, kp, a.Dout);
-    if (fn == nullptr) continue;
+    if (pick(a.loss_kind, ar, L, R, kp, a.Dout) == nullptr) continue;
     const double cost = model_cycles(L, R, kp, a.Dout);
     if (cost < best_cost) {
       best_cost = cost;
-      best.fn = fn;
-      best.L = L;
-      best.R = R;
-      best.kp = kp;
+      c->engine = kEngWave;
+      c->L = L;
+      c->R = R;
+      c->kp = kp;
+      c->x_width = lanes * kp;
     }
   }
-  return best;
+  return best_cost < 1e30;
 }
 
-}  // namespace
-bool linear_wave_supported(const FusedMlpArgs& a, const PersistArgs& p) { return choose(a, p).fn != nullptr; }
-
-void linear_wave_layout(const FusedMlpArgs& a, const PersistArgs& p, int* L, int* R, int* kp) {
-  const Choice c = choose(a, p);
-  *L = c.L;
-  *R = c.R;
-  *kp = c.kp;
-}
-
-hipError_t linear_wave_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out) {
-  const Choice c = choose(a, p);
-  if (c.fn == nullptr) return hipErrorInvalidValue;
-  out->fn = c.fn;
-  out->threads = kThreads;
-  out->a = a;
-  out->p = p;
-  out->p.loss_ring = 0;
-  out->lds = lds_bytes(a, p);
-  if (c.L == 0 && out->lds + ring_bytes(a, p) + kStaticLds <= 160 * 1024) {
-    out->p.loss_ring = 1;
-    out->lds += ring_bytes(a, p);
+hipError_t linear_wave_prepare(PersistLaunch* L) {
+  const FusedMlpArgs& a = L->a;
+  const PersistChoice& c = L->choice;
+  size_t lds = lds_bytes(a, L->p);
+  L->p.loss_ring = 0;
+  if (c.L == 0 && lds + ring_bytes(a, L->p) + kStaticLds <= 160 * 1024) {
+    L->p.loss_ring = 1;
+    lds += ring_bytes(a, L->p);
   }
-  if (out->lds > 64 * 1024)
-    PTDT_HIP_CHECK(hipFuncSetAttribute(c.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)out->lds));
-  return hipSuccess;
-}
-
-hipError_t linear_wave_persistent(const FusedMlpArgs& a, const PersistArgs& p, hipStream_t s) {
-  PersistLaunch L;
-  PTDT_HIP_CHECK(linear_wave_prepare(a, p, &L));
-  return persistent_launch(L, p.n_steps, p.cursor_host_pos, s);
+  return persist_set_kernel(L, pick(a.loss_kind, a.ar.world > 1, c.L, c.R, c.kp, a.Dout), kThreads, lds);
 }
 
 }  // namespace ptdt

@@ -45,8 +45,9 @@ bool mlp_tp_supported(const FusedMlpArgs& a, const PersistArgs& p) {
   return tp_lds_bytes(a, p, tp_bf16(p)) <= 160 * 1024;
 }
 
-hipError_t mlp_tp_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLaunch* out) {
-  if (!mlp_tp_supported(a, p)) return hipErrorInvalidValue;
+hipError_t mlp_tp_prepare(PersistLaunch* L) {
+  const FusedMlpArgs& a = L->a;
+  const PersistArgs& p = L->p;
   const bool vx = tp_vec_x(a);
   const bool st = p.stamps != nullptr;
   const bool ar = a.ar.world > 1;
@@ -58,14 +59,8 @@ hipError_t mlp_tp_prepare(const FusedMlpArgs& a, const PersistArgs& p, PersistLa
     fn = ar ? (vx ? pick_loss_tp<true, true>(a.loss_kind, mt, st) : pick_loss_tp<true, false>(a.loss_kind, mt, st))
             : (vx ? pick_loss_tp<false, true>(a.loss_kind, mt, st) : pick_loss_tp<false, false>(a.loss_kind, mt, st));
   }
-  const size_t lds = tp_lds_bytes(a, p, tp_bf16(p));
-  if (lds > 64 * 1024) PTDT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  out->fn = fn;
-  out->threads = 64 * (a.H / 16 + 1);  // compute waves + the helper wave
-  out->lds = lds;
-  out->a = a;
-  out->p = p;
-  return hipSuccess;
+  // threads: compute waves + the helper wave
+  return persist_set_kernel(L, fn, 64 * (L->choice.waves + 1), tp_lds_bytes(a, p, tp_bf16(p)));
 }
 
 }  // namespace ptdt

@@ -172,23 +172,13 @@ class FusedMLPStep:
         order from DeviceDataLoader.device_indices) replaces the in-kernel
         permutation; the steps must then stay inside that epoch, starting at
         step ``cursor_j``."""
-        if self.xgmi is None and self.comm is not None and self.comm.world > 1:
-            raise RuntimeError("the persistent engine needs the xGMI all-reduce for world > 1")
-        ce_index = self.loss_kind == LOSS_KINDS["ce_index"]
-        vid = self._vid(variant)
-        X, padded = self._wave_input(X, batch_size, sampler, vid)
+        # no list cache: every launch recomputes its epoch lists, as a one-off launch always has
+        plan = self._plan(X, Y, batch_size, sampler, cursor, losses, variant, idx, stamps, None, 0)
         done = 0
         while done < n_steps:
             n = min(max_steps_per_launch, n_steps - done)
-            self._C.fused_mlp_persistent(
-                X, None if ce_index else Y, Y if ce_index else None, self.P, self.G, self.mom, self.opt_step,
-                batch_size, self.Din, self.H, self.Dout, self.loss_kind, self.ignore_index, self.has_bias,
-                self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov,
-                self.xgmi.handle if self.xgmi is not None else None, n, sampler.num_replicas, sampler.rank,
-                sampler.num_samples, sampler.shuffle, sampler.seed, cursor, losses, stamps, vid, padded,
-                idx, cursor_j + done if idx is not None else -1)
+            plan.launch(n, cursor_j + done if idx is not None else -1)
             done += n
-        self._pending = False
 
     def persistent_plan(self, X, Y, batch_size: int, sampler, cursor: torch.Tensor, losses: torch.Tensor,
                         variant: str | None = None, idx: torch.Tensor | None = None,
@@ -201,12 +191,6 @@ class FusedMLPStep:
         with ``j`` the step in it) or ``[E, num_samples]`` for epochs
         ``idx_e0 .. idx_e0+E-1`` (``launch(n, pos)`` with ``pos = epoch * S + step``,
         the launch staying inside those epochs)."""
-        if self.xgmi is None and self.comm is not None and self.comm.world > 1:
-            raise RuntimeError("the persistent engine needs the xGMI all-reduce for world > 1")
-        ce_index = self.loss_kind == LOSS_KINDS["ce_index"]
-        vid = self._vid(variant)
-        X, padded = self._wave_input(X, batch_size, sampler, vid)
-        self._pending = False
         # launch-to-launch cache of the epoch index lists (tags -1: empty): a launch
         # starting inside an already computed epoch copies its list
         stride = (sampler.num_samples + 3) // 4 * 4
@@ -214,6 +198,16 @@ class FusedMLPStep:
         if idx is None:
             lcache = torch.zeros(2 * stride + 2, dtype=torch.int32, device=self.device)
             lcache[-2:] = -1
+        return self._plan(X, Y, batch_size, sampler, cursor, losses, variant, idx, stamps, lcache, idx_e0)
+
+    def _plan(self, X, Y, batch_size, sampler, cursor, losses, variant, idx, stamps, lcache, idx_e0):
+        """The native ``PersistentPlan`` of :meth:`run_persistent` (no list cache) and :meth:`persistent_plan`."""
+        if self.xgmi is None and self.comm is not None and self.comm.world > 1:
+            raise RuntimeError("the persistent engine needs the xGMI all-reduce for world > 1")
+        ce_index = self.loss_kind == LOSS_KINDS["ce_index"]
+        vid = self._vid(variant)
+        X, padded = self._wave_input(X, batch_size, sampler, vid)
+        self._pending = False
         return self._C.PersistentPlan(
             X, None if ce_index else Y, Y if ce_index else None, self.P, self.G, self.mom, self.opt_step,
             batch_size, self.Din, self.H, self.Dout, self.loss_kind, self.ignore_index, self.has_bias,
@@ -236,13 +230,9 @@ class FusedMLPStep:
     def _wave_input(self, X, batch_size, sampler, vid):
         """The wave engine reads whole lane chunks (L lanes x K features per row):
         when L*K > Din, hand it a zero-padded copy of X (cached per tensor version)."""
-        eng = self._C.persistent_engine(batch_size, self.Din, self.H, self.Dout, self.loss_kind,
-                                        sampler.num_samples, sampler.num_replicas, vid, self.has_bias)
-        if not eng.startswith("wave"):
-            return X, False
-        lanes, kp = int(eng.split("L")[1].split("R")[0]), int(eng.split("K")[1])
-        width = (lanes or 4) * kp  # L0: layout F, 4 feature groups
-        if width <= self.Din:
+        width = self._C.persistent_choice(batch_size, self.Din, self.H, self.Dout, self.loss_kind,
+                                          sampler.num_samples, sampler.num_replicas, vid, self.has_bias).x_width
+        if width <= self.Din:  # 0: not the wave engine
             return X, False
         key = (X.data_ptr(), X._version, tuple(X.shape), width)
         cached = getattr(self, "_xpad", None)

@@ -153,6 +153,44 @@ def test_persistent_engine_selection():
     assert C.persistent_engine(128, 20, 0, 1, ce_soft, 2048, 1) == "workgroup"  # B > 64
     assert C.persistent_engine(32, 20, 0, 10, ce_index, 2048, 1) == "workgroup"  # Dout 10 not instantiated
     assert C.persistent_engine(32, 20, 0, 1, ce_soft, 2048, 1, 1) == "workgroup"  # forced
+    # limits of each engine and refused forced variants: (B, Din, H, Dout, loss, num_samples, world, variant,
+    # has_bias) -> (name, x_width). The query names a workgroup engine where a plan would refuse.
+    mse, wave, wave_rows, wave_f, mfma, tp, tp_bf16 = 2, 2, 3, 4, 5, 6, 7
+    for cfg, name, x_width in [
+        ((64, 20, 0, 1, ce_soft, 2048, 1, 0, True), "wave:L0R4K5", 20),  # B = 64: 4 rows per slot
+        ((65, 20, 0, 1, ce_soft, 2048, 1, 0, True), "workgroup", 0),
+        ((32, 64, 0, 1, ce_soft, 2048, 1, 0, True), "wave:L0R2K16", 64),  # widest: 4 lanes x 16 features
+        ((32, 65, 0, 1, ce_soft, 2048, 1, 0, True), "workgroup", 0),
+        ((32, 18, 0, 1, ce_soft, 2048, 1, 0, True), "wave:L0R2K5", 20),  # rows zero-padded from 18 to 20
+        ((32, 33, 0, 2, mse, 2048, 1, wave_rows, True), "wave:L4R2K10", 40),  # padded from 33 to 40
+        ((17, 31, 0, 1, ce_soft, 2048, 2, wave_f, True), "wave:L0R2K8", 32),
+        ((32, 20, 0, 1, ce_soft, 20000, 1, 0, True), "wave:L0R2K5", 20),  # long epoch lists still fit
+        ((32, 20, 0, 4, ce_index, 2048, 1, 0, True), "workgroup", 0),  # no kernel for this (features per lane, Dout)
+        ((16, 20, 0, 1, ce_soft, 256, 8, 0, True), "wave:L0R1K5", 20),
+        ((16, 20, 0, 1, ce_soft, 256, 9, 0, True), "workgroup", 0),  # more ranks than the exchange holds
+        ((32, 20, 0, 10, ce_index, 2048, 1, wave, True), "workgroup", 0),  # forced wave, refused
+        ((32, 20, 16, 10, ce_index, 2048, 1, wave, True), "workgroup", 0),  # forced wave with a hidden layer
+        ((65, 20, 0, 1, ce_soft, 2048, 1, wave_f, True), "workgroup", 0),  # forced layout F, refused
+        ((32, 31, 64, 10, ce_index, 2048, 1, 0, True), "tp:4waves", 0),  # Din + bias = 32
+        ((32, 32, 64, 10, ce_index, 2048, 1, tp, True), "workgroup", 0),  # forced tp, Din + bias = 33
+        ((33, 20, 64, 10, ce_index, 2048, 1, 0, True), "workgroup", 0),  # B > 32: neither tp nor mfma
+        ((33, 20, 64, 10, ce_index, 2048, 1, tp, True), "workgroup", 0),
+        ((33, 20, 64, 10, ce_index, 2048, 1, mfma, True), "workgroup", 0),  # forced mfma, refused
+        ((32, 20, 80, 10, ce_index, 2048, 1, 0, True), "workgroup", 0),  # H > 64
+        ((32, 20, 64, 16, ce_index, 2048, 1, 0, True), "tp:4waves", 0),
+        ((32, 20, 64, 17, ce_index, 2048, 1, 0, True), "workgroup", 0),  # Dout > 16
+        ((32, 20, 64, 10, ce_index, 20000, 1, 0, True), "workgroup:mfma", 0),  # epoch lists too long for tp's LDS
+        ((32, 20, 64, 10, ce_index, 20000, 1, mfma, True), "workgroup:mfma", 0),
+        ((32, 20, 64, 10, ce_index, 2048, 9, 0, True), "workgroup:mfma", 0),  # 9 ranks: not tp
+        ((32, 20, 64, 10, ce_index, 2048, 8, tp, True), "tp:4waves", 0),
+        ((32, 20, 48, 10, ce_index, 2048, 1, tp_bf16, True), "tp_bf16:3waves", 0),
+        ((32, 20, 80, 10, ce_index, 2048, 1, tp_bf16, True), "workgroup", 0),  # forced tp_bf16, refused
+        ((32, 20, 0, 1, ce_soft, 2048, 1, tp, True), "workgroup", 0),  # forced tp without a hidden layer
+        ((8, 4, 16, 1, mse, 1, 1, 0, False), "tp:1waves", 0),
+    ]:
+        assert C.persistent_engine(*cfg) == name, cfg
+        choice = C.persistent_choice(*cfg)
+        assert (choice.name, choice.x_width) == (name, x_width), cfg
 
 
 def test_fused_adam_state_dict_resume_and_torch_interchange():

@@ -193,6 +193,50 @@ def test_persistent_plan_launch_at_equals_device_cursor(dev, kind):
     assert torch.equal(res[0], res[1])
 
 
+@pytest.mark.parametrize("kind,variant,engine", [
+    ("linear", None, "wave:L0R1K5"), ("linear", "wave_rows", "wave:L4R1K5"), ("mlp", None, "tp:1waves"),
+    ("mlp_bf16", None, "tp_bf16:1waves"), ("mlp", "mfma", "workgroup:mfma"), ("mlp", "workgroup", "workgroup"),
+])
+def test_run_persistent_equals_plan_launches(dev, kind, variant, engine):
+    """run_persistent (a plan without list cache, chunks of max_steps_per_launch) and
+    persistent_plan + launch(4), launch(3) run bitwise the same 7 steps on every engine:
+    S = 3 steps per epoch, so they cross two epoch boundaries. The plan reports the engine it
+    prepared, in the query's format."""
+    from pytorch_distributed_training_tutorials_amd.data.device_sampler import DeviceDistributedSampler
+    from pytorch_distributed_training_tutorials_amd.models.toy import ToyMLP, ddp_toy_model
+    from pytorch_distributed_training_tutorials_amd.ops.fused_step import FusedMLPStep
+
+    N, B = 48, 16
+    torch.manual_seed(11)
+    X = torch.randn(N, 20, device=dev)
+    if kind == "linear":
+        Y, mk, loss = torch.rand(N, 1, device=dev), (lambda: ddp_toy_model()), "ce_soft"
+    else:
+        Y, mk, loss = torch.randint(0, 10, (N,), device=dev), (lambda: ToyMLP(20, 16, 10)), "ce_index"
+    res = []
+    for mode in ("run", "plan"):
+        torch.manual_seed(7)
+        eng = FusedMLPStep(mk().to(dev), loss=loss, lr=0.05, momentum=0.9,
+                           dtype="bf16" if kind == "mlp_bf16" else "fp32")
+        sampler = DeviceDistributedSampler(N, 1, 0, seed=1, device=dev)
+        cursor = torch.zeros(2, dtype=torch.int32, device=dev)
+        losses = torch.zeros(4, device=dev)  # ends as steps [4, 5, 6, 3]: the second launch overwrites three
+        if mode == "run":
+            eng.run_persistent(X, Y, 7, B, sampler, cursor, losses, max_steps_per_launch=4, variant=variant)
+        else:
+            plan = eng.persistent_plan(X, Y, B, sampler, cursor, losses, variant=variant)
+            assert plan.engine == eng.persistent_engine(B, sampler, variant) == engine
+            plan.launch(4)
+            plan.launch(3)
+        torch.cuda.synchronize()
+        res.append((eng.P.clone(), eng.mom.clone(), losses, cursor.tolist()))
+    (P0, m0, l0, c0), (P1, m1, l1, c1) = res
+    assert torch.isfinite(P0).all() and not torch.equal(P0, torch.zeros_like(P0))
+    assert torch.equal(P0, P1) and torch.equal(m0, m1)
+    assert torch.equal(l0, l1) and torch.isfinite(l0).all()
+    assert c0 == c1 == [7 // 3, 7 % 3]
+
+
 @pytest.mark.parametrize("kind", ["mlp", "linear", "linear_nopair", "linear_rows"])
 def test_persistent_engine_two_ranks_one_gpu(tmp_path, kind):
     world = 2
