@@ -61,6 +61,9 @@ def main(argv=None):
                          "of steps)")
     ap.add_argument("--no_cudnn_benchmark", action="store_true",
                     help="keep MIOpen's heuristic solver choice (default: exhaustive find per conv shape)")
+    ap.add_argument("--sync_bn", action="store_true",
+                    help="cross-rank BatchNorm statistics: ops.norm.SyncBatchNorm (native) or torch.nn.SyncBatchNorm "
+                         "(--impl torch); PTDT_SYNCBN_FORCE=1 takes the synchronised path on one GPU too")
     a = ap.parse_args(argv)
     torch.backends.cudnn.benchmark = not a.no_cudnn_benchmark and not a.deterministic
     torch.backends.cudnn.deterministic = a.deterministic
@@ -81,6 +84,13 @@ def main(argv=None):
     model = resnet50(num_classes=1000).to(dev)
     if not a.no_channels_last:
         model = model.to(memory_format=torch.channels_last)
+    if a.sync_bn:  # before the DDP wrap: the converted layers keep the parameter tensors
+        if a.impl == "native":
+            from pytorch_distributed_training_tutorials_amd.ops.norm import SyncBatchNorm
+
+            model = SyncBatchNorm.convert_sync_batchnorm(model, comm=comm)
+        else:
+            model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
     if a.impl == "native":
         ddp = DistributedDataParallel(model, device_ids=[dev.index], comm=comm, bucket_cap_mb=a.bucket_cap_mb)
         opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4,
@@ -101,6 +111,10 @@ def main(argv=None):
         # RCCL collectives captured in a replayed step have only run at world 1 (RCCL refuses two
         # ranks on one GPU, so no one-GPU rehearsal exists): the default stays eager across GPUs;
         # --graph on or PTDT_GRAPH_MULTI=1 opts in
+        mode = "off"
+    if mode == "auto" and a.sync_bn:
+        # the synchronised layers put two collectives per BatchNorm into the step; capturing them has
+        # failed intermittently (profiles/syncbn.md), so --sync_bn stays eager unless --graph on asks
         mode = "off"
     graphed = mode != "off"
     from pytorch_distributed_training_tutorials_amd.utils.graphs import GraphedStep
@@ -212,7 +226,7 @@ def main(argv=None):
             "dtype": a.dtype, "data": "synthetic ImageNet-shaped (generated on device)",
             "config": {"model": "resnet50", "per_device_batch": a.batch_size, "image": a.image,
                        "parallelism": f"dp{world}", "channels_last": not a.no_channels_last},
-            "impl": a.impl, "hipgraph": graphed, "graph_mode": mode, **({"ab_ms_per_step": ab} if ab else {}), "bn_dir": os.environ.get("PTDT_BN_DIR", "0"), "miopen_find": "exhaustive (cudnn.benchmark)" if torch.backends.cudnn.benchmark else "heuristic",
+            "impl": a.impl, "sync_bn": a.sync_bn, "hipgraph": graphed, "graph_mode": mode, **({"ab_ms_per_step": ab} if ab else {}), "bn_dir": os.environ.get("PTDT_BN_DIR", "0"), "miopen_find": "exhaustive (cudnn.benchmark)" if torch.backends.cudnn.benchmark else "heuristic",
             "buckets_MB": [round(b / 2 ** 20, 2) for b in ddp.bucket_sizes_bytes()] if a.impl == "native" else None,
             **({"loss_curve": [round(float(v), 4) for v in curve]} if a.loss_curve else {}),
             **({"graph": graph_info} if graph_info else {}),

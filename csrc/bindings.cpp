@@ -1390,6 +1390,164 @@ std::vector<Tensor> bn_bwd_reduce(Tensor dy, Tensor x, c10::optional<Tensor> wei
   return {g, dw, db, dwb.narrow(0, 2, 3)};
 }
 
+// ---- cross-rank statistics (ops.norm.SyncBatchNorm)
+double* f64_of(const Tensor& t, const Tensor& x, int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() && t.scalar_type() == at::kDouble && t.is_contiguous() &&
+                  t.numel() == numel,
+              "batchnorm: ", name, " must be a contiguous float64 tensor of ", numel, " elements on x's device");
+  return t.data_ptr<double>();
+}
+
+// This rank's record (local mean[C], M2[C], row count) into rec[2 C + 1] (float64, written in place).
+void bn_sync_stats_(Tensor x, Tensor rec, c10::optional<Tensor> tickets) {
+  int64_t M;
+  int C;
+  bn_rows(x, &M, &C);
+  c10::hip::HIPGuard guard(x.device().index());
+  double* r = f64_of(rec, x, 2 * (int64_t)C + 1, "rec");
+  Tensor ws = at::empty({bn_workspace_floats(M, C, dt_of(x))}, x.options().dtype(at::kFloat));
+  hip_check(bn_sync_stats(x.data_ptr(), dt_of(x), M, C, ws.data_ptr<float>(),
+                          bn_tickets(x, tickets, bn_num_tickets(C, dt_of(x))), r, cur_stream(x)),
+            "bn_sync_stats");
+}
+
+// Merge of the gathered records [W, 2 C + 1]: returns (stats[4, C], count[1] float64 = global rows);
+// running statistics and num_batches_tracked updated.
+std::vector<Tensor> bn_sync_merge_(Tensor rec, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
+                                   c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
+                                   c10::optional<Tensor> num_batches_tracked, double momentum, double eps) {
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kDouble && rec.is_contiguous() && rec.dim() == 2 &&
+                  rec.size(0) >= 1 && rec.size(1) >= 3 && rec.size(1) % 2 == 1,
+              "batchnorm: rec must be the gathered [W, 2 C + 1] float64 records");
+  const int W = (int)rec.size(0), C = (int)((rec.size(1) - 1) / 2);
+  c10::hip::HIPGuard guard(rec.device().index());
+  Tensor stats = at::empty({4, C}, rec.options().dtype(at::kFloat));
+  Tensor count = at::empty({1}, rec.options());
+  BnParams p{};
+  p.weight = opt_f32(weight, C, "weight");
+  p.bias = opt_f32(bias, C, "bias");
+  p.running_mean = const_cast<float*>(opt_f32(running_mean, C, "running_mean"));
+  p.running_var = const_cast<float*>(opt_f32(running_var, C, "running_var"));
+  TORCH_CHECK((p.running_mean == nullptr) == (p.running_var == nullptr), "batchnorm: running_mean/var together");
+  if (num_batches_tracked.has_value() && num_batches_tracked->defined()) {
+    TORCH_CHECK(num_batches_tracked->is_cuda() && num_batches_tracked->scalar_type() == at::kLong &&
+                num_batches_tracked->numel() == 1, "batchnorm: num_batches_tracked must be a 1-element int64 tensor");
+    p.num_batches_tracked = num_batches_tracked->data_ptr<int64_t>();
+  }
+  p.momentum = (float)momentum;
+  p.eps = (float)eps;
+  float* st = stats.data_ptr<float>();
+  p.mean = st;
+  p.invstd = st + C;
+  p.scale = st + 2 * C;
+  p.shift = st + 3 * C;
+  hip_check(bn_sync_merge(rec.data_ptr<double>(), W, C, p, count.data_ptr<double>(), cur_stream(rec)),
+            "bn_sync_merge");
+  return {stats, count};
+}
+
+// Backward reduce pass with the global statistics: returns (g, dweight, dbias, sums[2, C] float64) --
+// the LOCAL sums (to be all-reduced) and the LOCAL parameter gradients.
+std::vector<Tensor> bn_sync_bwd_reduce(Tensor dy, Tensor x, c10::optional<Tensor> weight, Tensor stats, bool relu,
+                                       bool want_dweight, c10::optional<Tensor> tickets,
+                                       c10::optional<Tensor> dweight_out, c10::optional<Tensor> dbias_out,
+                                       c10::optional<Tensor> dy2, c10::optional<Tensor> mask) {
+  int64_t M;
+  int C;
+  bn_rows(x, &M, &C);
+  same_rows(dy, x, "dy");
+  c10::hip::HIPGuard guard(x.device().index());
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == 4 * C,
+              "batchnorm: stats must be the [4, C] forward statistics");
+  BnBwdArgs a{};
+  a.dy = dy.data_ptr();
+  if (dy2.has_value() && dy2->defined()) {
+    same_rows(*dy2, x, "dy2");
+    a.dy2 = dy2->data_ptr();
+  }
+  a.x = x.data_ptr();
+  if (relu && mask.has_value() && mask->defined()) {
+    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte &&
+                    mask->numel() == M * C / (x.scalar_type() == at::kFloat ? 4 : 8),
+                "batchnorm: mask must be the forward's [M*C/V] byte mask");
+    a.mask = mask->data_ptr<uint8_t>();
+  }
+  Tensor g = at::empty_like(x);
+  Tensor dwb = at::empty({2, C}, x.options().dtype(at::kFloat));
+  Tensor sums = at::empty({2, C}, x.options().dtype(at::kDouble));
+  Tensor ws = at::empty({bn_workspace_floats(M, C, dt_of(x))}, x.options().dtype(at::kFloat));
+  a.dres = g.data_ptr();
+  a.reduce_only = 1;
+  a.dtype = dt_of(x);
+  a.M = M;
+  a.C = C;
+  a.relu = relu ? 1 : 0;
+  a.workspace = ws.data_ptr<float>();
+  a.tickets = bn_tickets(x, tickets, bn_num_tickets(C, a.dtype));
+  const float* st = stats.data_ptr<float>();
+  a.p.weight = opt_f32(weight, C, "weight");
+  a.p.mean = st;
+  a.p.invstd = st + C;
+  a.p.scale = st + 2 * C;
+  a.p.shift = st + 3 * C;
+  float* d = dwb.data_ptr<float>();
+  a.p.dweight = want_dweight ? d : nullptr;
+  a.p.dbias = want_dweight ? d + C : nullptr;
+  Tensor dw_out, db_out;
+  if (want_dweight && dweight_out.has_value() && dweight_out->defined()) {
+    a.p.dweight = const_cast<float*>(opt_f32(dweight_out, C, "dweight_out"));
+    dw_out = *dweight_out;
+  }
+  if (want_dweight && dbias_out.has_value() && dbias_out->defined()) {
+    a.p.dbias = const_cast<float*>(opt_f32(dbias_out, C, "dbias_out"));
+    db_out = *dbias_out;
+  }
+  hip_check(bn_sync_backward_reduce(a, sums.data_ptr<double>(), cur_stream(x)), "bn_sync_backward_reduce");
+  Tensor dw = want_dweight ? (dw_out.defined() ? dw_out : dwb[0]) : Tensor();
+  Tensor db = want_dweight ? (db_out.defined() ? db_out : dwb[1]) : Tensor();
+  return {g, dw, db, sums};
+}
+
+// coef[3, C] of dx = A g + B x + C from the all-reduced sums[2, C] and the global row count[1].
+Tensor bn_sync_coef_(Tensor sums, Tensor count, c10::optional<Tensor> weight, Tensor stats) {
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.dim() == 2 &&
+                  stats.size(0) == 4,
+              "batchnorm: stats must be the [4, C] forward statistics");
+  const int C = (int)stats.size(1);
+  c10::hip::HIPGuard guard(stats.device().index());
+  const double* sm = f64_of(sums, stats, 2 * (int64_t)C, "sums");
+  const double* cnt = f64_of(count, stats, 1, "count");
+  Tensor coef = at::empty({3, C}, stats.options());
+  BnBwdParams p{};
+  const float* st = stats.data_ptr<float>();
+  p.weight = opt_f32(weight, C, "weight");
+  p.mean = st;
+  p.invstd = st + C;
+  float* d = coef.data_ptr<float>();
+  p.coef_a = d;
+  p.coef_b = d + C;
+  p.coef_c = d + 2 * C;
+  hip_check(bn_sync_coef(sm, cnt, C, p, cur_stream(stats)), "bn_sync_coef");
+  return coef;
+}
+
+// dx = coef[0] g + coef[1] x + coef[2] per channel (the backward's apply pass over a materialised g).
+Tensor bn_bwd_apply_g(Tensor g, Tensor x, Tensor coef) {
+  int64_t M;
+  int C;
+  bn_rows(x, &M, &C);
+  same_rows(g, x, "g");
+  c10::hip::HIPGuard guard(x.device().index());
+  TORCH_CHECK(coef.is_cuda() && coef.device() == x.device() && coef.scalar_type() == at::kFloat &&
+                  coef.is_contiguous() && coef.numel() == 3 * (int64_t)C,
+              "batchnorm: coef must be [3, C] float");
+  Tensor dx = at::empty_like(x);
+  hip_check(bn_backward_apply_g(g.data_ptr(), x.data_ptr(), dx.data_ptr(), dt_of(x), coef.data_ptr<float>(), M, C,
+                                cur_stream(x)),
+            "bn_backward_apply_g");
+  return dx;
+}
+
 bool conv1x1_bwd_supported_(int64_t K, int64_t N) { return conv1x1_bwd_supported((int)K, (int)N); }
 
 // Backward of BN(conv1x1(x)) from bn_bwd_reduce's (g, coef): returns (dx [M, K], dw [N, K]) in bf16.
@@ -1641,6 +1799,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("maxpool2d_bwd", &maxpool2d_bwd);
   m.def("bn_fwd_apply", &bn_fwd_apply, py::arg("x"), py::arg("stats"), py::arg("residual"), py::arg("relu"),
         py::arg("want_mask"));
+  m.def("bn_sync_stats", &bn_sync_stats_, "this rank's BN record (mean[C], M2[C], rows) into rec[2C+1] float64",
+        py::arg("x"), py::arg("rec"), py::arg("tickets") = py::none());
+  m.def("bn_sync_merge", &bn_sync_merge_, "gathered records [W, 2C+1] -> (stats[4, C], global row count[1])",
+        py::arg("rec"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"));
+  m.def("bn_sync_bwd_reduce", &bn_sync_bwd_reduce, "BN backward reduce, raw: (g, dweight, dbias, sums[2, C] float64)",
+        py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("stats"), py::arg("relu"), py::arg("want_dweight"),
+        py::arg("tickets") = py::none(), py::arg("dweight_out") = py::none(), py::arg("dbias_out") = py::none(),
+        py::arg("dy2") = py::none(), py::arg("mask") = py::none());
+  m.def("bn_sync_coef", &bn_sync_coef_, "coef[3, C] from the all-reduced sums and the global row count",
+        py::arg("sums"), py::arg("count"), py::arg("weight"), py::arg("stats"));
+  m.def("bn_bwd_apply_g", &bn_bwd_apply_g, "dx = coef[0] g + coef[1] x + coef[2]", py::arg("g"), py::arg("x"),
+        py::arg("coef"));
   m.def("conv1x1_bn_stats", &conv1x1_bn_stats, py::arg("x"), py::arg("w"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("num_batches_tracked"), py::arg("momentum"),
         py::arg("eps"), py::arg("tickets"), py::arg("tile") = 256);

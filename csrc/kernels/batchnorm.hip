@@ -324,10 +324,22 @@ __device__ __forceinline__ void rearm(int* ticket) {
   __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <typename T>
+// Cross-rank statistics (SyncBatchNorm, ops/norm.py). SYNC / RAW instances of the two reduction
+// kernels stop before the local row count finalises anything: the last block writes this rank's
+// float64 record instead, the ranks exchange the records, and bn_sync_merge_kernel /
+// bn_sync_coef_kernel finish with the global count. The parameter blocks extend the local ones, so
+// the sweeps, the partial hand-off and the combine are the same code.
+struct BnSyncParams : BnParams {
+  double* rec;  // [2 C + 1]: local mean[C], M2[C] = sum (x - local mean)^2, row count
+};
+struct BnSyncBwdParams : BnBwdParams {
+  double* sums;  // [2, C]: local sum g, sum g (x - mean) about the GLOBAL mean
+};
+
+template <typename T, bool SYNC = false>
 __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x, int64_t M, int C, int TC, int RPI,
                                                         int64_t rows_per_block, int il, float* ws, int* tickets,
-                                                        BnParams p) {
+                                                        std::conditional_t<SYNC, BnSyncParams, BnParams> p) {
   constexpr int V = VecIO<T>::V;
   constexpr int U = 8;  // rows in flight per thread
   extern __shared__ float sh[];  // 2 x RPI x TC*V reduction slots, then the last-block flag
@@ -387,6 +399,19 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
   if (!last_block(tickets + blockIdx.y, flag, (p.fence_handoff != 0))) return;
   double s, q;
   combine_partials(ws, (int)gridDim.x, C, blockIdx.y * width, width, sh, s, q, (p.fence_handoff != 0));
+  if constexpr (SYNC) {  // this rank's record; invstd and the running statistics wait for the merge
+    if (tid < width && c < C) {
+      double m2 = q - s * s / (double)M;
+      if (m2 < 0.0) m2 = 0.0;
+      p.rec[c] = (double)Cvt<T>::load(x, c) + s / (double)M;
+      p.rec[C + c] = m2;
+    }
+    if (tid == 0) {
+      rearm(tickets + blockIdx.y);
+      if (blockIdx.y == 0) p.rec[2 * C] = (double)M;
+    }
+    return;
+  }
   if (tid < width && c < C) {
     const double Kc = (double)Cvt<T>::load(x, c);
     const double ms = s / (double)M;
@@ -409,6 +434,68 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
     rearm(tickets + blockIdx.y);  // for the next launch (stream order)
     if (blockIdx.y == 0 && p.num_batches_tracked) *p.num_batches_tracked += 1;
   }
+}
+
+// Merge of the W gathered records ([W, 2 C + 1], rank-major) into the [4, C] statistics the apply
+// and backward passes consume; one thread per channel, Chan's pairwise update in rank order, in
+// double. Every rank merges the same bytes in the same order: statistics and running buffers come
+// out bitwise identical across ranks. `count` receives the global row count N (the backward's
+// coefficient pass reads it there: no host round trip). A rank with no rows is skipped.
+__global__ void __launch_bounds__(kThreads) bn_sync_merge_kernel(const double* __restrict__ rec, int W, int C,
+                                                                 BnParams p, double* __restrict__ count) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const int64_t slot = 2 * (int64_t)C + 1;
+  double n = 0.0, mean = 0.0, m2 = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const double* rr = rec + r * slot;
+    const double nb = rr[2 * C];
+    if (!(nb > 0.0)) continue;
+    const double mb = rr[c], m2b = rr[C + c];
+    if (n == 0.0) {
+      n = nb;
+      mean = mb;
+      m2 = m2b;
+    } else {
+      const double na = n, d = mb - mean;
+      n = na + nb;
+      mean = mean + d * nb / n;
+      m2 = m2 + m2b + d * d * na * nb / n;
+    }
+  }
+  const double var = n > 0.0 ? m2 / n : 0.0;
+  const float invstd = (float)(1.0 / sqrt(var + (double)p.eps));
+  const float w = p.weight ? p.weight[c] : 1.f, b = p.bias ? p.bias[c] : 0.f;
+  p.mean[c] = (float)mean;
+  p.invstd[c] = invstd;
+  p.scale[c] = w * invstd;
+  p.shift[c] = b - (float)mean * w * invstd;
+  if (p.running_mean) {
+    const double unbiased = n > 1.0 ? m2 / (n - 1.0) : var;
+    p.running_mean[c] = (float)((1.0 - p.momentum) * p.running_mean[c] + p.momentum * mean);
+    p.running_var[c] = (float)((1.0 - p.momentum) * p.running_var[c] + p.momentum * unbiased);
+  }
+  if (c == 0) {
+    *count = n;
+    if (p.num_batches_tracked) *p.num_batches_tracked += 1;
+  }
+}
+
+// dx = A g + B x + C coefficients from the all-reduced sums ([2, C]: sum g, sum g (x - mean)) and
+// the global row count: bn_bwd_reduce_kernel's formulas with M replaced by N
+__global__ void __launch_bounds__(kThreads) bn_sync_coef_kernel(const double* __restrict__ sums,
+                                                                const double* __restrict__ count, int C,
+                                                                BnBwdParams p) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const double N = *count;
+  const double sdy = sums[c], sdx = sums[C + c];
+  const double invstd = p.invstd[c], mean = p.mean[c];
+  const double w = p.weight ? p.weight[c] : 1.0;
+  const double k = w * invstd, s1 = sdy / N, s2 = invstd * invstd * sdx / N;
+  p.coef_a[c] = (float)k;
+  p.coef_b[c] = (float)(-k * s2);
+  p.coef_c[c] = (float)(k * s2 * mean - k * s1);
 }
 
 // MASKOUT: also write the ReLU mask, one byte per V-vector (bit v: y > 0), for a backward that
@@ -480,13 +567,16 @@ __device__ __forceinline__ float round_to(float v) {
 // GOUT: the masked gradient g = mask (dy + dy2), rounded to T, is also written (to gout): it IS
 // the residual gradient, and the apply pass then reads g and x only (bn_bwd_apply_g_kernel)
 // instead of dy, dy2, x and the mask. The sums use the rounded g, so both passes agree.
-template <typename T, int MASK, bool ADD2, bool GOUT = false>
+// RAW (cross-rank statistics): mean / invstd are the global ones; the last block writes the local
+// sums as float64 (for the all-reduce) and the LOCAL parameter gradients, and no coefficients.
+template <typename T, int MASK, bool ADD2, bool GOUT = false, bool RAW = false>
 __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ dy2,
                                                              const T* __restrict__ x,
                                                              const T* __restrict__ y, const uint8_t* __restrict__ mk,
                                                              T* __restrict__ gout, int64_t M, int C, int TC,
                                                              int RPI, int64_t rows_per_block, int il, float* ws,
-                                                             int* tickets, BnBwdParams p) {
+                                                             int* tickets,
+                                                             std::conditional_t<RAW, BnSyncBwdParams, BnBwdParams> p) {
   constexpr int V = VecIO<T>::V;
   constexpr int U = 4;  // rows in flight per thread (x 2-3 loads each)
   extern __shared__ float sh[];
@@ -579,6 +669,16 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
   if (!last_block(tickets + blockIdx.y, flag, (p.fence_handoff != 0))) return;
   double sdy, sdx;
   combine_partials(ws, (int)gridDim.x, C, blockIdx.y * width, width, sh, sdy, sdx, (p.fence_handoff != 0));
+  if constexpr (RAW) {
+    if (tid < width && c < C) {
+      p.sums[c] = sdy;
+      p.sums[C + c] = sdx;
+      if (p.dweight) p.dweight[c] = (float)(sdx * (double)p.invstd[c]);
+      if (p.dbias) p.dbias[c] = (float)sdy;
+    }
+    if (tid == 0) rearm(tickets + blockIdx.y);
+    return;
+  }
   if (tid < width && c < C) {
     const double invstd = p.invstd[c], mean = p.mean[c];
     const double w = p.weight ? p.weight[c] : 1.0;
@@ -843,6 +943,61 @@ hipError_t bwd_impl(const BnBwdArgs& a, hipStream_t s) {
   return bwd_launch2<T, 2>(a, g, s);
 }
 
+// ---- cross-rank statistics (SyncBatchNorm): launches of the SYNC / RAW instances
+template <typename T>
+hipError_t sync_stats_impl(const void* x, int64_t M, int C, float* ws, int* tickets, double* rec, int fence,
+                           hipStream_t s) {
+  if (C % VecIO<T>::V != 0) return hipErrorInvalidValue;
+  const Geom g = geom<T>(M, C);
+  BnSyncParams p{};
+  p.rec = rec;
+  p.fence_handoff = fence;
+  hipLaunchKernelGGL((bn_stats_kernel<T, true>), dim3(g.gx, g.gy), dim3(kRed), red_lds<T>(), s,
+                     static_cast<const T*>(x), M, C, g.TC, g.RPI, g.rows_per_block,
+                     interleave_rows() | (dir(1) << 1), ws, tickets, p);
+  return hipGetLastError();
+}
+
+template <typename T, int MASK, bool ADD2>
+hipError_t sync_reduce_launch(const BnBwdArgs& a, double* sums, hipStream_t s) {
+  const Geom g = geom<T>(a.M, a.C);
+  BnSyncBwdParams p{};
+  static_cast<BnBwdParams&>(p) = a.p;
+  p.sums = sums;
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, MASK, ADD2, true, true>), dim3(g.gx, g.gy), dim3(kRed), red_lds<T>(), s,
+                     static_cast<const T*>(a.dy), static_cast<const T*>(a.dy2), static_cast<const T*>(a.x),
+                     static_cast<const T*>(nullptr), a.mask, static_cast<T*>(a.dres), a.M, a.C, g.TC, g.RPI,
+                     g.rows_per_block, interleave_rows() | (dir(4) << 1), a.workspace, a.tickets, p);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t sync_reduce_impl(const BnBwdArgs& a, double* sums, hipStream_t s) {
+  if (a.C % VecIO<T>::V != 0 || a.dres == nullptr) return hipErrorInvalidValue;
+  const bool add2 = a.dy2 != nullptr;
+  if (!a.relu) return add2 ? sync_reduce_launch<T, 0, true>(a, sums, s) : sync_reduce_launch<T, 0, false>(a, sums, s);
+  if (a.mask != nullptr)
+    return add2 ? sync_reduce_launch<T, 3, true>(a, sums, s) : sync_reduce_launch<T, 3, false>(a, sums, s);
+  if (a.p.scale == nullptr || a.p.shift == nullptr) return hipErrorInvalidValue;
+  return add2 ? sync_reduce_launch<T, 2, true>(a, sums, s) : sync_reduce_launch<T, 2, false>(a, sums, s);
+}
+
+template <typename T>
+hipError_t apply_g_impl(const void* g, const void* x, void* dx, const float* coef, int64_t M, int C, hipStream_t s) {
+  constexpr int V = VecIO<T>::V;
+  if (C % V != 0) return hipErrorInvalidValue;
+  const int64_t nvec = M * C / V;
+  BnBwdParams p{};
+  p.coef_a = const_cast<float*>(coef);
+  p.coef_b = const_cast<float*>(coef) + C;
+  p.coef_c = const_cast<float*>(coef) + 2 * C;
+  const dim3 grid(apply_grid(nvec)), blk(kThreads);
+  return with_au([&](auto au) {
+    hipLaunchKernelGGL((bn_bwd_apply_g_kernel<T, decltype(au)::value>), grid, blk, (size_t)3 * C * sizeof(float), s,
+                       static_cast<const T*>(g), static_cast<const T*>(x), static_cast<T*>(dx), p, nvec, C, dir(8));
+  });
+}
+
 }  // namespace
 
 int64_t bn_workspace_floats(int64_t M, int C, int dtype) {
@@ -881,6 +1036,40 @@ hipError_t bn_backward(const BnBwdArgs& a0, hipStream_t s) {
   BnBwdArgs a = a0;
   a.p.fence_handoff = fence_handoff();
   return a.dtype == kF32 ? bwd_impl<float>(a, s) : bwd_impl<uint16_t>(a, s);
+}
+
+hipError_t bn_sync_stats(const void* x, int dtype, int64_t M, int C, float* workspace, int* tickets, double* rec,
+                         hipStream_t s) {
+  if (M <= 0 || C <= 0) return hipErrorInvalidValue;
+  return dtype == kF32 ? sync_stats_impl<float>(x, M, C, workspace, tickets, rec, fence_handoff(), s)
+                       : sync_stats_impl<uint16_t>(x, M, C, workspace, tickets, rec, fence_handoff(), s);
+}
+
+hipError_t bn_sync_merge(const double* rec, int W, int C, const BnParams& p, double* count, hipStream_t s) {
+  if (W <= 0 || C <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((C + kThreads - 1) / kThreads), dim3(kThreads), 0, s, rec, W, C, p,
+                     count);
+  return hipGetLastError();
+}
+
+hipError_t bn_sync_backward_reduce(const BnBwdArgs& a0, double* sums, hipStream_t s) {
+  if (a0.M <= 0 || a0.C <= 0) return hipErrorInvalidValue;
+  BnBwdArgs a = a0;
+  a.p.fence_handoff = fence_handoff();
+  return a.dtype == kF32 ? sync_reduce_impl<float>(a, sums, s) : sync_reduce_impl<uint16_t>(a, sums, s);
+}
+
+hipError_t bn_sync_coef(const double* sums, const double* count, int C, const BnBwdParams& p, hipStream_t s) {
+  if (C <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bn_sync_coef_kernel, dim3((C + kThreads - 1) / kThreads), dim3(kThreads), 0, s, sums, count, C,
+                     p);
+  return hipGetLastError();
+}
+
+hipError_t bn_backward_apply_g(const void* g, const void* x, void* dx, int dtype, const float* coef, int64_t M, int C,
+                               hipStream_t s) {
+  if (M <= 0 || C <= 0) return hipErrorInvalidValue;
+  return dtype == kF32 ? apply_g_impl<float>(g, x, dx, coef, M, C, s) : apply_g_impl<uint16_t>(g, x, dx, coef, M, C, s);
 }
 
 }  // namespace ptdt

@@ -474,6 +474,24 @@ int64_t bn_workspace_floats(int64_t M, int C, int dtype);
 int bn_num_tickets(int C, int dtype);
 hipError_t bn_forward_train(const BnFwdArgs& a, hipStream_t s);
 hipError_t bn_backward(const BnBwdArgs& a, hipStream_t s);
+// Cross-rank statistics (SyncBatchNorm): each reduction stops before the local row count
+// finalises it, the ranks exchange float64 records, and two one-thread-per-channel kernels finish.
+//   forward:  bn_sync_stats -> all-gather of rec[2 C + 1] -> bn_sync_merge -> bn_forward_train(stats_ready)
+//   backward: bn_sync_backward_reduce -> all-reduce of sums[2, C] -> bn_sync_coef -> bn_backward_apply_g
+// rec = local mean[C], M2[C] (sum of squared deviations about it), row count. bn_sync_merge fills
+// p.mean/invstd/scale/shift from the W records (Chan's update in rank order, double), updates the
+// running statistics with the global unbiased variance and stores the global row count in `count`.
+// bn_sync_backward_reduce: as a reduce_only bn_backward (a.dres receives g; workspace and tickets
+// as there), but sums = local sum g, sum g (x - mean); p.dweight/dbias (optional) get the LOCAL
+// gradients; no coefficients. bn_sync_coef writes p.coef_a/b/c from the all-reduced sums and
+// *count. bn_backward_apply_g: dx = coef[0] g + coef[1] x + coef[2] (coef [3, C]).
+hipError_t bn_sync_stats(const void* x, int dtype, int64_t M, int C, float* workspace, int* tickets, double* rec,
+                         hipStream_t s);
+hipError_t bn_sync_merge(const double* rec, int W, int C, const BnParams& p, double* count, hipStream_t s);
+hipError_t bn_sync_backward_reduce(const BnBwdArgs& a, double* sums, hipStream_t s);
+hipError_t bn_sync_coef(const double* sums, const double* count, int C, const BnBwdParams& p, hipStream_t s);
+hipError_t bn_backward_apply_g(const void* g, const void* x, void* dx, int dtype, const float* coef, int64_t M, int C,
+                               hipStream_t s);
 // Backward of BN(conv1x1(x)) for the streaming shapes (csrc/kernels/conv1x1_bwd.hip): dY = A g + B y + C
 // (coef = [A; B; C], 3 x N floats, from a reduce_only bn_backward) feeds dX = dY W and dW = dY^T X
 // without storing dY. g, y: [M, N] bf16; x: [M, K]; w: [N, K]; dx: [M, K]; dw: [N, K] bf16.

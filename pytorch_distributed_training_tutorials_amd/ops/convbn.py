@@ -42,7 +42,7 @@ import torch.nn as nn
 
 from .._ext import native
 from .conv import cast_weight
-from .norm import BatchNorm2d, batch_norm_act
+from .norm import BatchNorm2d, batch_norm_act, synchronizing
 
 _MODE = os.environ.get("PTDT_CONVBN", "auto")  # auto: per-shape timing decides; on / 1: always; off / 0: never
 _ENABLED = _MODE not in ("0", "off")
@@ -117,6 +117,8 @@ class _Conv1x1StatsFn(torch.autograd.Function):
 
 def _fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual) -> bool:
     if not (_ENABLED and isinstance(bn, BatchNorm2d) and bn.training and bn.momentum is not None):
+        return False
+    if synchronizing(bn):  # the epilogue's statistics (and the ConvBwdLink backward) are this rank's only
         return False
     if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None

@@ -16,6 +16,10 @@ activation in bf16) and the backward's reduce pass writes the masked gradient
 Eval mode applies the running statistics in one launch. Anything else (NCHW,
 CPU, momentum=None, odd channel counts) uses PyTorch's batch_norm with the same
 semantics. Parameters, buffers and state_dict keys are nn.BatchNorm2d's.
+
+``SyncBatchNorm`` is the same layer with training statistics over every rank of a
+communicator: the reductions stop at a float64 record, the records are exchanged
+(one all-gather forward, one all-reduce backward) and merged on the device.
 """
 from __future__ import annotations
 
@@ -105,6 +109,45 @@ class ResidualLink:
             t.record_stream(cur)
 
 
+def _bwd_inputs(ctx, dy, x, mask, weight):
+    """Head shared by the fused BN backwards (local and cross-rank statistics): the incoming gradient in
+    x's layout, the linked second addend, what is wanted, and the DDP grad sinks."""
+    want_dw = weight is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+    link_in, link_out = ctx.link_in, ctx.link_out
+    # a bit mask is read by the backward's materialised-gradient path, which writes the
+    # residual gradient: request it whenever the mask exists
+    want_dres = ctx.has_res and (ctx.needs_input_grad[3] or link_in is not None or mask is not None)
+    dy = _like(dy, x)
+    dy2 = None
+    if link_out is not None:  # a later block's residual gradient of our output
+        # (None: that block's backward did not run -- its output does not reach the loss)
+        dy2 = link_out.take(dy.device)
+        if dy2 is not None and dy2.stride() != dy.stride():
+            dy, dy2 = dy + dy2, None
+    sinks = [None, None]
+    if want_dw:  # DDP grad sinks (ops/conv.py): write dweight/dbias straight into the bucket slots
+        for k, p in enumerate(ctx.params):
+            if p is not None and p.grad is None and getattr(p, "_ptdt_grad_sink", None) is not None:
+                sinks[k] = p._ptdt_grad_sink()
+    return dy, dy2, want_dw, want_dres, sinks
+
+
+def _bwd_outputs(ctx, dx, dw, db, dres, want_dw, n_rest):
+    """Tail shared by the fused BN backwards: the residual gradient goes to the residual's producer
+    through the link where one is free, else to autograd; ``n_rest`` non-tensor forward arguments."""
+    link_in = ctx.link_in
+    if link_in is not None and dres is not None:  # delivered to the residual's producer instead of autograd
+        if link_in.dres is None:
+            link_in.put(dres)
+            dres = None
+        elif not ctx.needs_input_grad[3]:  # the link is taken (another consumer delivered): sum into it
+            link_in.put(dres)
+            dres = None
+        # else: autograd adds this one (returned below), as _GradLinkFn does
+    return (dx if ctx.needs_input_grad[0] else None, dw if want_dw else None, db if want_dw else None,
+            dres if (dres is not None and ctx.needs_input_grad[3]) else None, *([None] * n_rest))
+
+
 class _BatchNormActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, nbt, relu: bool, momentum: float,
@@ -130,23 +173,7 @@ class _BatchNormActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, mask, weight, stats = ctx.saved_tensors
-        want_dw = weight is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        link_in, link_out = ctx.link_in, ctx.link_out
-        # a bit mask is read by the backward's materialised-gradient path, which writes the
-        # residual gradient: request it whenever the mask exists
-        want_dres = ctx.has_res and (ctx.needs_input_grad[3] or link_in is not None or mask is not None)
-        dy = _like(dy, x)
-        dy2 = None
-        if link_out is not None:  # a later block's residual gradient of our output
-            # (None: that block's backward did not run -- its output does not reach the loss)
-            dy2 = link_out.take(dy.device)
-            if dy2 is not None and dy2.stride() != dy.stride():
-                dy, dy2 = dy + dy2, None
-        sinks = [None, None]
-        if want_dw:  # DDP grad sinks (ops/conv.py): write dweight/dbias straight into the bucket slots
-            for k, p in enumerate(ctx.params):
-                if p is not None and p.grad is None and getattr(p, "_ptdt_grad_sink", None) is not None:
-                    sinks[k] = p._ptdt_grad_sink()
+        dy, dy2, want_dw, want_dres, sinks = _bwd_inputs(ctx, dy, x, mask, weight)
         clink = ctx.conv_link
         if clink is not None and ctx.needs_input_grad[0]:
             # reduce pass only: the producing 1x1 conv applies dY = A g + B x + C inside its fused
@@ -157,16 +184,7 @@ class _BatchNormActFn(torch.autograd.Function):
         else:
             dx, dw, db, dres = native().bn_bwd(dy, x, None, weight, stats, ctx.relu, want_dres, want_dw,
                                                ctx.tickets, sinks[0], sinks[1], dy2, mask)
-        if link_in is not None and dres is not None:  # delivered to the residual's producer instead of autograd
-            if link_in.dres is None:
-                link_in.put(dres)
-                dres = None
-            elif not ctx.needs_input_grad[3]:  # the link is taken (another consumer delivered): sum into it
-                link_in.put(dres)
-                dres = None
-            # else: autograd adds this one (returned below), as _GradLinkFn does
-        return (dx if ctx.needs_input_grad[0] else None, dw if want_dw else None, db if want_dw else None,
-                dres if (dres is not None and ctx.needs_input_grad[3]) else None, *([None] * 11))
+        return _bwd_outputs(ctx, dx, dw, db, dres, want_dw, 11)
 
 
 class _GradLinkFn(torch.autograd.Function):
@@ -207,6 +225,13 @@ def _tickets_of(bn, x):
     return t
 
 
+def _native_ok(x: torch.Tensor, residual) -> bool:
+    """The native kernels take ``x`` (and ``residual``, in the same layout)."""
+    return _rows_layout_ok(x) and (residual is None or (residual.dtype == x.dtype and residual.shape == x.shape
+                                                        and residual.stride() == x.stride()
+                                                        and residual.data_ptr() % 16 == 0))
+
+
 def batch_norm_act(x: torch.Tensor, bn: nn.modules.batchnorm._BatchNorm, residual: torch.Tensor | None = None,
                    relu: bool = False, link: bool = False, stats: torch.Tensor | None = None,
                    conv_link=None) -> torch.Tensor:
@@ -220,9 +245,7 @@ def batch_norm_act(x: torch.Tensor, bn: nn.modules.batchnorm._BatchNorm, residua
     ``stats``: this batch's [4, C] statistics (mean, invstd, scale, shift) already computed --
     and the running statistics already updated -- by the kernel that produced ``x``
     (ops/convbn.py); only the apply pass runs. Training mode, native layout only."""
-    fast = _rows_layout_ok(x) and (residual is None or (residual.dtype == x.dtype and residual.shape == x.shape
-                                                        and residual.stride() == x.stride()
-                                                        and residual.data_ptr() % 16 == 0))
+    fast = _native_ok(x, residual)
     use_batch_stats = bn.training or not bn.track_running_stats
     if fast and use_batch_stats and bn.momentum is not None:
         track = bn.training and bn.track_running_stats
@@ -277,6 +300,224 @@ class BatchNorm2d(nn.BatchNorm2d):
     def forward(self, x, residual=None, relu: bool = False, link: bool = False):
         self._check_input_dim(x)
         return batch_norm_act(x, self, residual, relu, link)
+
+
+# ----------------------------------------------------------------------------- cross-rank statistics
+# Protocol (docs/ARCHITECTURE.md "SyncBatchNorm"): every rank reduces its rows to a float64 record
+# [mean[C], M2[C], rows]; the records are all-gathered and merged in rank order (Chan's update), so
+# every rank holds bitwise the same statistics; the backward all-reduces the two per-channel sums
+# (sum g, sum g (x - mean)). The parameter gradients stay local: DDP averages them.
+class _SyncBatchNormActFn(torch.autograd.Function):
+    """``_BatchNormActFn`` with the statistics of the whole world: three launches and one collective
+    around the local reduction in each direction, the same apply passes, links, mask and grad sinks."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var, nbt, relu: bool, momentum: float,
+                eps: float, tickets, link_in, link_out, comm):
+        C = native()
+        ch = x.shape[1]
+        want_mask = relu and residual is not None
+        rec = torch.empty(2 * ch + 1, dtype=torch.float64, device=x.device)
+        C.bn_sync_stats(x, rec, tickets)
+        gathered = torch.empty(comm.world, 2 * ch + 1, dtype=torch.float64, device=x.device)
+        comm.all_gather(gathered.view(-1), rec)
+        stats, count = C.bn_sync_merge(gathered, weight, bias, running_mean, running_var, nbt, momentum, eps)
+        y, mask = C.bn_fwd_apply(x, stats, residual, relu, want_mask)
+        ctx.tickets = tickets
+        ctx.params = (weight, bias)
+        ctx.relu = relu
+        ctx.has_res = residual is not None
+        ctx.link_in, ctx.link_out = link_in, link_out
+        ctx.comm = comm
+        ctx.save_for_backward(x, mask if want_mask else None, weight, stats, count)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mask, weight, stats, count = ctx.saved_tensors
+        dy, dy2, want_dw, want_dres, sinks = _bwd_inputs(ctx, dy, x, mask, weight)
+        C = native()
+        g, dw, db, sums = C.bn_sync_bwd_reduce(dy, x, weight, stats, ctx.relu, want_dw, ctx.tickets, sinks[0],
+                                               sinks[1], dy2, mask)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            ctx.comm.all_reduce(sums)
+            dx = C.bn_bwd_apply_g(g, x, C.bn_sync_coef(sums, count, weight, stats))
+        return _bwd_outputs(ctx, dx, dw, db, g if want_dres else None, want_dw, 10)
+
+
+def _merge_records(rec: torch.Tensor):
+    """(rows, mean, M2) of the whole world from the gathered ``[W, 2 C + 1]`` records: Chan's pairwise
+    update in rank order, as csrc/kernels/batchnorm.hip's merge kernel."""
+    ch = (rec.shape[1] - 1) // 2
+    n, mean, m2 = rec[0, 2 * ch], rec[0, :ch], rec[0, ch:2 * ch]
+    for r in range(1, rec.shape[0]):
+        nb, mb, m2b = rec[r, 2 * ch], rec[r, :ch], rec[r, ch:2 * ch]
+        na, d = n, mb - mean
+        n = na + nb
+        mean = mean + d * nb / n
+        m2 = m2 + m2b + d * d * na * nb / n
+    return n, mean, m2
+
+
+class _SyncBatchNormRefFn(torch.autograd.Function):
+    """The same protocol in plain torch ops (CPU tensors, NCHW, channel counts that do not
+    vector-align): returns (normalised x, global mean, global unbiased variance)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps: float, comm):
+        ch = x.shape[1]
+        dims = [d for d in range(x.dim()) if d != 1]
+        shape = [1, ch] + [1] * (x.dim() - 2)
+        rows = x.numel() // max(ch, 1)
+        xd = x.detach().double()
+        rec = torch.zeros(2 * ch + 1, dtype=torch.float64, device=x.device)
+        if rows > 0:
+            rec[:ch] = xd.mean(dims)
+            rec[ch:2 * ch] = (xd - rec[:ch].view(shape)).square().sum(dims)
+            rec[2 * ch] = rows
+        gathered = torch.empty(comm.world, 2 * ch + 1, dtype=torch.float64, device=x.device)
+        comm.all_gather(gathered.view(-1), rec)
+        if bool((gathered[:, 2 * ch] < 1).any()):  # every rank sees it: all raise together
+            empty = [r for r in range(comm.world) if float(gathered[r, 2 * ch]) < 1]
+            raise ValueError(f"SyncBatchNorm: every rank must contribute at least one row; rank(s) {empty} "
+                             "passed an empty batch")
+        n, mean, m2 = _merge_records(gathered)
+        invstd = torch.rsqrt(m2 / n + eps)
+        mean32, invstd32 = mean.float(), invstd.float()
+        xhat = (x.detach().float() - mean32.view(shape)) * invstd32.view(shape)
+        y = xhat
+        if weight is not None:
+            y = y * weight.detach().float().view(shape)
+        if bias is not None:
+            y = y + bias.detach().float().view(shape)
+        ctx.comm, ctx.shape, ctx.dims = comm, shape, dims
+        ctx.save_for_backward(xhat, weight, invstd32, n)
+        unbiased = (m2 / torch.clamp(n - 1, min=1.0)).float()
+        ctx.mark_non_differentiable(mean32, unbiased)
+        return y.to(x.dtype), mean32, unbiased
+
+    @staticmethod
+    def backward(ctx, dy, _gmean, _gvar):
+        xhat, weight, invstd, n = ctx.saved_tensors
+        shape, dims = ctx.shape, ctx.dims
+        g = dy.float()
+        # the protocol's sums: sum g and sum g (x - mean) = sum g xhat / invstd
+        sums = torch.stack([g.sum(dims), (g * xhat).sum(dims) / invstd]).double()
+        db = sums[0].float() if ctx.needs_input_grad[2] else None
+        dw = (sums[1].float() * invstd) if ctx.needs_input_grad[1] else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            ctx.comm.all_reduce(sums)
+            s1 = (sums[0] / n).float().view(shape)
+            s2 = (sums[1] / n).float().view(shape) * invstd.view(shape)  # invstd sum g (x - mean) / N
+            k = invstd.view(shape) if weight is None else (weight.detach().float() * invstd).view(shape)
+            dx = (k * (g - xhat * s2 - s1)).to(dy.dtype)
+        return dx, dw, db, None, None
+
+
+def _force_sync() -> bool:
+    return __import__("os").environ.get("PTDT_SYNCBN_FORCE", "0") == "1"
+
+
+def synchronizing(bn: nn.Module) -> bool:
+    """True for a :class:`SyncBatchNorm` whose next forward takes cross-rank statistics. Whatever
+    computes local statistics on a BatchNorm2d's behalf (ops/convbn.py's conv epilogue, the fused
+    stem below) must decline for it."""
+    return isinstance(bn, SyncBatchNorm) and bn.synchronizing()
+
+
+class SyncBatchNorm(BatchNorm2d):
+    """:class:`BatchNorm2d` whose training statistics span every rank of ``comm`` (default:
+    ``parallel.comm.get_default()``, resolved at the first training forward). Same parameters,
+    buffers, state_dict keys and ``forward(x, residual, relu, link)``; the residual / ReLU epilogues,
+    the bit mask, the residual links and the DDP grad sinks are kept. Eval mode and a 1-rank world
+    are the parent's code path (``PTDT_SYNCBN_FORCE=1`` synchronises at world 1 too, so one GPU can
+    run the exchange through real collectives). Every rank must contribute at least one row.
+
+    The exchange runs outside the kernels; 1-D / 3-D inputs and statistics from a 1x1 conv's epilogue
+    are not covered (a synchronising layer takes the separate statistics pass)."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, momentum: float | None = 0.1, affine: bool = True,
+                 track_running_stats: bool = True, comm=None, device=None, dtype=None):
+        super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
+        self._comm = comm
+        self.sync_forwards = 0  # forwards that took cross-rank statistics (tests, diagnostics)
+
+    @property
+    def comm(self):
+        if self._comm is None:
+            from ..parallel import comm as comm_mod
+
+            self._comm = comm_mod.get_default()
+        return self._comm
+
+    def synchronizing(self) -> bool:
+        if not self.training:
+            return False
+        if _force_sync():
+            return True
+        if self._comm is None:  # a 1-rank job needs no communicator
+            from ..parallel import env
+
+            if env.world_size() == 1:
+                return False
+        return self.comm.world > 1
+
+    def forward(self, x, residual=None, relu: bool = False, link: bool = False):
+        self._check_input_dim(x)
+        if not self.synchronizing():
+            return batch_norm_act(x, self, residual, relu, link)
+        self.sync_forwards += 1
+        comm = self.comm
+        track = self.track_running_stats
+        if _native_ok(x, residual) and self.momentum is not None:
+            link_in = getattr(residual, "_ptdt_res_link", None) if (link and residual is not None) else None
+            link_out = ResidualLink() if torch.is_grad_enabled() else None
+            y = _SyncBatchNormActFn.apply(x, self.weight, self.bias, residual, self.running_mean if track else None,
+                                          self.running_var if track else None,
+                                          self.num_batches_tracked if track else None, relu, float(self.momentum),
+                                          float(self.eps), _tickets_of(self, x), link_in, link_out, comm)
+            if link_out is not None:
+                y._ptdt_res_link = link_out
+            return y
+        y, mean, unbiased = _SyncBatchNormRefFn.apply(x, self.weight, self.bias, float(self.eps), comm)
+        if track:
+            with torch.no_grad():
+                self.num_batches_tracked.add_(1)
+                m = self.momentum if self.momentum is not None else 1.0 / float(self.num_batches_tracked)
+                self.running_mean.mul_(1.0 - m).add_(mean.to(self.running_mean.dtype), alpha=m)
+                self.running_var.mul_(1.0 - m).add_(unbiased.to(self.running_var.dtype), alpha=m)
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if relu else y
+
+    @classmethod
+    def convert_sync_batchnorm(cls, module: nn.Module, comm=None) -> nn.Module:
+        """Replace every ``nn.BatchNorm2d`` under (and including) ``module`` -- ops.norm.BatchNorm2d
+        too -- by a :class:`SyncBatchNorm` holding the SAME parameter and buffer tensors and
+        ``training`` flag; an existing SyncBatchNorm is left alone. Returns the (possibly new) root.
+        Convert before wrapping in DDP, as with ``torch.nn.SyncBatchNorm``."""
+        if isinstance(module, cls):
+            return module
+        if isinstance(module, nn.BatchNorm2d):
+            ref = module.weight if module.weight is not None else module.running_mean
+            new = cls(module.num_features, module.eps, module.momentum, module.affine, module.track_running_stats,
+                      comm=comm, device=ref.device if ref is not None else None)
+            for name, p in module._parameters.items():
+                new._parameters[name] = p
+            for name, b in new._buffers.items():  # ticket buffers a plain nn.BatchNorm2d does not bring
+                if name not in module._buffers and b is not None and ref is not None:
+                    new._buffers[name] = b.to(ref.device)
+            for name, b in module._buffers.items():  # the ticket buffers of an ops BatchNorm2d included
+                new._buffers[name] = b
+            new.training = module.training
+            return new
+        for name, child in module.named_children():
+            new = cls.convert_sync_batchnorm(child, comm)
+            if new is not child:
+                setattr(module, name, new)
+        return module
 
 
 # ----------------------------------------------------------------------------- pooling
@@ -352,7 +593,7 @@ def bn_relu_maxpool(x: torch.Tensor, bn: nn.Module, pool: nn.MaxPool2d) -> torch
     channels_last GPU activation (PTDT_BN_POOL=0 disables), composed otherwise."""
     cfg = _pool_cfg(pool, x) if _BN_POOL else None
     if (cfg is None or not isinstance(bn, BatchNorm2d) or not bn.training or bn.momentum is None
-            or not _rows_layout_ok(x)):
+            or not _rows_layout_ok(x) or synchronizing(bn)):  # the fused statistics are this rank's only
         y = bn(x, relu=True) if isinstance(bn, BatchNorm2d) else torch.relu(bn(x))
         return pool(y)
     track = bn.track_running_stats

@@ -299,6 +299,14 @@ class HostStagedComm:
         t.copy_(h)
         return t
 
+    def all_gather(self, out, inp, stream=None):
+        """``out`` is ``[world * inp.numel()]`` (rank-major), as :meth:`Communicator.all_gather`."""
+        h = inp.detach().reshape(-1).cpu()
+        ho = torch.empty(self.world * h.numel(), dtype=h.dtype)
+        dist.all_gather_into_tensor(ho, h)
+        out.copy_(ho.view_as(out))
+        return out
+
     def all_gather_object(self, obj):
         out = [None] * self.world
         dist.all_gather_object(out, obj)
