@@ -765,6 +765,8 @@ void gemm_big_(Tensor A, Tensor Bt, Tensor C, c10::optional<Tensor> bias, bool r
 Tensor relu_bwd(Tensor dy, Tensor y) {
   check_gpu(dy, "dy");
   check_gpu(y, "y");
+  TORCH_CHECK(y.scalar_type() == dy.scalar_type() && y.numel() == dy.numel() && y.device() == dy.device(),
+              "relu_bwd: dy and y must share dtype, size and device");
   c10::hip::HIPGuard guard(dy.device().index());
   Tensor dx = at::empty_like(dy);
   hip_check(relu_backward(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dt_of(dy), dy.numel(), cur_stream(dy)),

@@ -49,8 +49,14 @@ __global__ void __launch_bounds__(kBlock) ce_fwd_kernel(const T* __restrict__ lo
     lse_out[2 * B + b] = ts;  // row sum of soft targets, reused by the backward
     float l;
     if (soft) {
-      // -sum_c t_c * (z_c - lse), label smoothing mixes in the uniform target
-      l = -(tz - lse * ts);
+      // -sum_c t_c * (z_c - lse), label smoothing mixes in the uniform target. The product is rounded on
+      // its own: contracted into an fma it leaves tz's rounding error behind, and the single-class case
+      // ([B, 1] logits with float targets, lse == z) would not be exactly zero
+      {
+#pragma clang fp contract(off)
+        const float lt = lse * ts;
+        l = lt - tz;
+      }
       if (ls > 0.f) l = (1.f - ls) * l + ls * (lse - zsum / (float)C);
       row_loss[b] = l;
     } else {

@@ -44,8 +44,11 @@ class _CrossEntropyFn(torch.autograd.Function):
 def cross_entropy(input: torch.Tensor, target: torch.Tensor, ignore_index: int = -100,
                   label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
     """Mean-reduced cross entropy over ``[B, C]`` logits with soft (float
-    ``[B, C]``) or class-index (int64 ``[B]``) targets."""
-    if use_native(input) and input.dim() == 2 and reduction == "mean":
+    ``[B, C]``) or class-index (int64 ``[B]``) targets. The kernels take float32 and
+    bfloat16 logits (the loss is a float32 scalar for both); other dtypes, shapes and
+    reductions go to ``F.cross_entropy``, as in :func:`mse_loss`."""
+    if use_native(input) and input.dim() == 2 and reduction == "mean" \
+            and input.dtype in (torch.float32, torch.bfloat16):
         if target.is_floating_point() and target.shape != input.shape:
             raise ValueError(f"soft targets must match logits {tuple(input.shape)}, got {tuple(target.shape)}")
         return _CrossEntropyFn.apply(input, target, ignore_index, float(label_smoothing))

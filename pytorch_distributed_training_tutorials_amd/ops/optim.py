@@ -10,8 +10,10 @@ names, per-parameter state keys ``momentum_buffer`` / ``exp_avg`` /
   * parameters that are back-to-back views of one flat buffer (FlatParameters,
     or DDP's grad buckets on the gradient side) -> ONE flat launch;
   * otherwise -> multi-tensor launches of <= 32 tensors each;
-  * the "first momentum step" and Adam's bias-correction step count live in a
-    device int32 counter, so ``step()`` is hipGraph-capturable (no host reads);
+  * the "first momentum step" and Adam's bias-correction step count live in
+    device int32 counters, so ``step()`` is hipGraph-capturable (no host reads);
+    one counter per cohort (:class:`_StepCounters`), so every parameter counts
+    its own updates as in ``torch.optim`` and a group may mix dtypes;
   * CPU parameters use eager ATen math (plumbing tests).
 """
 from __future__ import annotations
@@ -40,6 +42,53 @@ def _bf16_shadow(p: torch.Tensor) -> torch.Tensor:
     return sh
 
 
+class _StepCounters:
+    """Device step counters, one per cohort: the parameters of one (group, device, dtype)
+    that have been updated in exactly the same steps. Parameters that start together stay
+    one cohort (one counter, one launch); a parameter that gets its first gradient later,
+    or misses a step, counts on its own from then on."""
+
+    def __init__(self):
+        self.counters: dict = {}  # cohort id -> int32[1] tensor on the cohort's device
+        self._of: dict = {}       # parameter -> cohort id
+        self._size: dict = {}     # cohort id -> number of member parameters
+
+    def _add(self, counter, members):
+        cid = len(self.counters)
+        self.counters[cid] = counter
+        self._size[cid] = len(members)
+        for p in members:
+            self._of[p] = cid
+        return counter
+
+    def count(self, p):
+        cid = self._of.get(p)
+        return None if cid is None else self.counters[cid]
+
+    def cohorts(self, ps, initial):
+        """Partition ``ps`` (the parameters of one (device, dtype) updated in this step) into
+        ``[(counter, members)]``. New parameters join one cohort per ``initial(p)`` value; a
+        cohort only partly in ``ps`` is split, the present part taking a copy of the count."""
+        old, new = {}, {}
+        for p in ps:
+            cid = self._of.get(p)
+            if cid is None:
+                new.setdefault(initial(p), []).append(p)
+            else:
+                old.setdefault(cid, []).append(p)
+        out = []
+        for cid, members in old.items():
+            counter = self.counters[cid]
+            if len(members) != self._size[cid]:
+                self._size[cid] -= len(members)
+                counter = self._add(counter.clone(), members)
+            out.append((counter, members))
+        for value, members in new.items():
+            counter = torch.full((1,), value, dtype=torch.int32, device=members[0].device)
+            out.append((self._add(counter, members), members))
+        return out
+
+
 class FusedSGD(Optimizer):
     """``bf16_shadow=True``: every f32 GPU parameter also gets a bf16 copy of its
     updated value, written by the same update kernel (``p._ptdt_bf16``); under bf16
@@ -56,19 +105,17 @@ class FusedSGD(Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                         nesterov=nesterov, maximize=maximize)
         super().__init__(params, defaults)
-        self._counters: dict = {}
-        self._flat_mom: dict = {}
+        self._cohorts = _StepCounters()
         self.bf16_shadow = bf16_shadow
 
-    def _counter(self, gi: int, device) -> torch.Tensor:
-        key = (gi, device)
-        c = self._counters.get(key)
-        if c is None:
-            started = any("momentum_buffer" in self.state[p] for p in self.param_groups[gi]["params"]
-                          if p.device == device)
-            c = torch.full((1,), 1 if started else 0, dtype=torch.int32, device=device)
-            self._counters[key] = c
-        return c
+    @property
+    def _counters(self) -> dict:
+        """The live device counters (a counter reads 0 until its cohort's first update)."""
+        return self._cohorts.counters
+
+    def _started(self, p) -> int:
+        """1 when a parameter new to this optimizer object already has a (loaded) momentum buffer."""
+        return int("momentum_buffer" in self.state[p])
 
     def _momentum_buffers(self, gi, ps):
         """Per-parameter momentum buffers; for flat parameter spans they are views
@@ -102,26 +149,30 @@ class FusedSGD(Optimizer):
                 if device.type != "cuda":
                     self._cpu_step(ps, lr, mu, damp, wd, nest, gscale)
                     continue
-                grads = [p.grad for p in ps]
-                step = self._counter(gi, device)  # before creating buffers: "first step" is decided here
-                moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
-                C = native()
-                pflat = contiguous_span([p.data for p in ps])
-                gflat = contiguous_span(grads)
-                mflat = contiguous_span(moms) if moms else None
-                pdata = [p.data for p in ps]
-                aligned = same_layout(pdata, grads) and (not moms or same_layout(pdata, moms))
-                shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and dtype == torch.float32) else []
-                if (dtype == torch.float32 and aligned and pflat is not None and gflat is not None
-                        and (not moms or mflat is not None) and not shadows):
-                    # one launch for the whole group (also increments the device counter)
-                    C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale)
-                else:
-                    C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows)
-                    step.add_(1)
-                for p in ps if shadows else ():
-                    p._ptdt_bf16_version = p._version  # the shadow is current until p changes
+                # before creating buffers: a parameter's "first step" is decided here
+                for step, cps in self._cohorts.cohorts(ps, self._started):
+                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale)
         return loss
+
+    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale):
+        grads = [p.grad for p in ps]
+        moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
+        C = native()
+        pflat = contiguous_span([p.data for p in ps])
+        gflat = contiguous_span(grads)
+        mflat = contiguous_span(moms) if moms else None
+        pdata = [p.data for p in ps]
+        aligned = same_layout(pdata, grads) and (not moms or same_layout(pdata, moms))
+        shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and dtype == torch.float32) else []
+        if (dtype == torch.float32 and aligned and pflat is not None and gflat is not None
+                and (not moms or mflat is not None) and not shadows):
+            # one launch for the whole cohort (also increments the device counter)
+            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale)
+        else:
+            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows)
+            step.add_(1)
+        for p in ps if shadows else ():
+            p._ptdt_bf16_version = p._version  # the shadow is current until p changes
 
     def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale):
         for p in ps:
@@ -147,7 +198,11 @@ class FusedAdam(Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                         decoupled_weight_decay=decoupled_weight_decay, maximize=maximize)
         super().__init__(params, defaults)
-        self._steps: dict = {}
+        self._cohorts = _StepCounters()
+
+    def _loaded_step(self, p) -> int:
+        """Updates a parameter new to this optimizer object already has behind it (a loaded state)."""
+        return int(float(self.state[p].get("step", 0)))
 
     def _state_lists(self, ps):
         need = [p for p in ps if "exp_avg" not in self.state[p]]
@@ -171,53 +226,46 @@ class FusedAdam(Optimizer):
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             gscale = -1.0 if group["maximize"] else 1.0
-            for (device, dtype), ps in _split_by_device(group["params"]).items():
-                key = (gi, device)
-                if key not in self._steps:
-                    self._steps[key] = torch.zeros(1, dtype=torch.int32, device=device)
-                step = self._steps[key]
-                step.add_(1)
-                ms, vs = self._state_lists(ps)
-                if device.type != "cuda":
-                    self._cpu_step(ps, ms, vs, step, group, gscale)
-                    continue
-                C = native()
-                grads = [p.grad for p in ps]
-                pflat, gflat = contiguous_span([p.data for p in ps]), contiguous_span(grads)
-                mflat, vflat = contiguous_span(ms), contiguous_span(vs)
-                pdata = [p.data for p in ps]
-                aligned = same_layout(pdata, grads) and same_layout(pdata, ms) and same_layout(pdata, vs)
-                if dtype == torch.float32 and aligned and None not in (pflat, gflat, mflat, vflat):
-                    C.adam_flat_(pflat, gflat, mflat, vflat, step, group["lr"], b1, b2, group["eps"],
-                                 group["weight_decay"], group["decoupled_weight_decay"], gscale)
-                else:
-                    C.adam_multi_([p.data for p in ps], grads, ms, vs, step, group["lr"], b1, b2, group["eps"],
-                                  group["weight_decay"], group["decoupled_weight_decay"], gscale)
+            for (device, dtype), sub in _split_by_device(group["params"]).items():
+                for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
+                    step.add_(1)
+                    ms, vs = self._state_lists(ps)
+                    if device.type != "cuda":
+                        self._cpu_step(ps, ms, vs, step, group, gscale)
+                        continue
+                    C = native()
+                    grads = [p.grad for p in ps]
+                    pflat, gflat = contiguous_span([p.data for p in ps]), contiguous_span(grads)
+                    mflat, vflat = contiguous_span(ms), contiguous_span(vs)
+                    pdata = [p.data for p in ps]
+                    aligned = same_layout(pdata, grads) and same_layout(pdata, ms) and same_layout(pdata, vs)
+                    if dtype == torch.float32 and aligned and None not in (pflat, gflat, mflat, vflat):
+                        C.adam_flat_(pflat, gflat, mflat, vflat, step, group["lr"], b1, b2, group["eps"],
+                                     group["weight_decay"], group["decoupled_weight_decay"], gscale)
+                    else:
+                        C.adam_multi_(pdata, grads, ms, vs, step, group["lr"], b1, b2, group["eps"],
+                                      group["weight_decay"], group["decoupled_weight_decay"], gscale)
         return loss
 
     def state_dict(self):
         """torch.optim.Adam layout: per parameter ``exp_avg``, ``exp_avg_sq`` and the
         bias-correction ``step`` (a float32 scalar tensor) -- the kernels keep the step
-        as one device counter per (group, device); it is copied into the state here."""
-        for gi, group in enumerate(self.param_groups):
-            for (device, _dtype), ps in _split_by_device(group["params"], False).items():
-                step = self._steps.get((gi, device))
-                for p in ps:
-                    if p in self.state:
-                        self.state[p]["step"] = torch.tensor(float(step.item()) if step is not None else 0.0)
+        in one device counter per cohort; it is copied into the state here."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p in self.state:
+                    step = self._cohorts.count(p)
+                    self.state[p]["step"] = torch.tensor(float(step.item()) if step is not None
+                                                         else float(self._loaded_step(p)))
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
         """Restores moments and the bias-correction step (a state_dict of this class or of
         torch.optim.Adam/AdamW), so a resumed run continues the same trajectory."""
         super().load_state_dict(state_dict)
-        self._steps = {}
-        for gi, group in enumerate(self.param_groups):
-            for (device, _dtype), ps in _split_by_device(group["params"], False).items():
-                steps = [self.state[p]["step"] for p in ps if "step" in self.state.get(p, {})]
-                if steps:
-                    self._steps[(gi, device)] = torch.full((1,), int(float(steps[0])), dtype=torch.int32,
-                                                           device=device)
+        self._cohorts = _StepCounters()  # the next step() starts each parameter at its loaded ``step``
+        for group in self.param_groups:
+            for ps in _split_by_device(group["params"], False).values():
                 # the kernels need the flat-state layout: pop every loaded moment of the split first,
                 # then re-home them in ONE flat allocation (per-parameter allocations would leave the
                 # group without a contiguous span and every later step on the slower multi-tensor path)
