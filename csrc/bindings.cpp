@@ -297,6 +297,11 @@ class PersistentPlan {
   int64_t capacity() const { return capacity_; }
   // query-format name (persistent_engine) of the engine this plan prepared
   const std::string& engine() const { return engine_; }
+  // which instantiation of the engine's kernel the plan launches (wave engine, layout F: "generic",
+  // "lean-plain", "lean-mom"; see linear_wave_variant); "" for the other engines
+  std::string kernel_variant() const {
+    return L_.choice.engine == kEngWave ? wave_variant_name(L_.kernel_variant) : "";
+  }
   ~PersistentPlan() {
     if (ev_) hipEventDestroy(ev_);
   }
@@ -428,6 +433,28 @@ PersistChoice persistent_choice(int64_t B, int64_t Din, int64_t H, int64_t Dout,
   pa.variant = (int)variant;
   pa.N = (int)std::max<int64_t>(num_samples, 1);
   return persistent_select(a, pa);
+}
+
+// The kernel variant (PersistentPlan.kernel_variant) a plan of this configuration would launch, under the
+// same assumptions as persistent_choice; momentum != 0 stands for "a momentum buffer exists".
+std::string persistent_kernel_variant(int64_t B, int64_t Din, int64_t H, int64_t Dout, int64_t loss_kind,
+                                      int64_t num_samples, int64_t world, int64_t variant, bool has_bias,
+                                      double momentum, double weight_decay, bool stamps) {
+  FusedMlpArgs a{};
+  a.B = (int)B; a.Din = (int)Din; a.H = (int)H; a.Dout = (int)Dout; a.loss_kind = (int)loss_kind;
+  a.has_bias = has_bias ? 1 : 0;
+  a.ar.world = (int)world;
+  a.ldx = kWaveLdxAny;
+  a.x_padded = 1;
+  a.momentum = (float)momentum;
+  a.weight_decay = (float)weight_decay;
+  PersistArgs pa{};
+  pa.num_samples = (int)num_samples;
+  pa.variant = (int)variant;
+  pa.N = (int)std::max<int64_t>(num_samples, 1);
+  const PersistChoice c = persistent_select(a, pa);
+  if (c.engine != kEngWave) return "";
+  return wave_variant_name(linear_wave_variant(a, pa, c, momentum != 0.0, stamps));
 }
 
 // ------------------------------------------------------------- torch-identical sampler orders
@@ -1702,6 +1729,7 @@ PYBIND11_MODULE(_C, m) {
       .def("launch_at", &PersistentPlan::launch_at, py::arg("n_steps"), py::arg("pos"))
       .def_property_readonly("capacity", &PersistentPlan::capacity)
       .def_property_readonly("engine", &PersistentPlan::engine)
+      .def_property_readonly("kernel_variant", &PersistentPlan::kernel_variant)
       .def("set_timeline", &PersistentPlan::set_timeline, py::arg("addr"))
       .def("last_launch_ns", &PersistentPlan::last_launch_ns)
       .def("launch_wait_at", &PersistentPlan::launch_wait_at, py::arg("n_steps"), py::arg("pos"), py::arg("mode"),
@@ -1737,6 +1765,10 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"), py::arg("loss_kind"), py::arg("num_samples"),
       py::arg("world"), py::arg("variant") = 0, py::arg("has_bias") = true);
+  m.def("persistent_kernel_variant", &persistent_kernel_variant, py::arg("B"), py::arg("Din"), py::arg("H"),
+        py::arg("Dout"), py::arg("loss_kind"), py::arg("num_samples"), py::arg("world"), py::arg("variant") = 0,
+        py::arg("has_bias") = true, py::arg("momentum") = 0.0, py::arg("weight_decay") = 0.0,
+        py::arg("stamps") = false);
   m.def("fused_mlp_lds_bytes", [](int B, int Din, int H, int Dout) { return fused_mlp_lds_bytes(B, Din, H, Dout); });
   m.def("sgd_flat_", &sgd_flat_);
   m.def("adam_flat_", &adam_flat_);

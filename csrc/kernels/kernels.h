@@ -153,6 +153,14 @@ struct PersistChoice {
 // a forced variant names one engine (tp_bf16 only ever forced) and gives kEngNone when that engine
 // does not support the configuration; a workgroup engine past the LDS bound gives kEngNone.
 PersistChoice persistent_select(const FusedMlpArgs& a, const PersistArgs& p);
+// Plan-time kernel variants of the wave engine's layout F (linear_wave_impl.h). The generic kernel
+// decides everything at run time; a lean one is the generic kernel minus the code its plan can never
+// run (other SGD kinds, the no-ring loss path, short-batch masks and scale selects, the stamps).
+// linear_wave_variant() is the only place that knows the rules.
+enum WaveKernelVariant : int { kWaveGeneric = 0, kWaveLeanPlain = 1, kWaveLeanMom = 2 };
+inline const char* wave_variant_name(int v) {
+  return v == kWaveLeanPlain ? "lean-plain" : (v == kWaveLeanMom ? "lean-mom" : "generic");
+}
 // A persistent launch resolved once (engine choice, kernel, LDS size, argument
 // checks): relaunching it only sets n_steps (and the explicit-list cursor) and
 // calls hipLaunchKernel, so a short run pays no per-call planning.
@@ -163,6 +171,7 @@ struct PersistLaunch {
   FusedMlpArgs a{};
   PersistArgs p{};
   PersistChoice choice{};       // what fused_mlp_persistent_prepare selected
+  int kernel_variant = kWaveGeneric;  // WaveKernelVariant of fn (wave engine; kWaveGeneric elsewhere)
   int64_t host_ns[2] = {0, 0};  // CLOCK_MONOTONIC right before / after the last hipLaunchKernel
 };
 // Timeline probe support (timeline.hip): thread 0 of wave 0 writes the realtime counter.
@@ -207,6 +216,9 @@ bool mlp_tp_supported(const FusedMlpArgs& a, const PersistArgs& p);
 bool mlp_mfma_supported(const FusedMlpArgs& a);
 hipError_t fused_mlp_check_dims(const FusedMlpArgs& a);
 hipError_t linear_wave_prepare(PersistLaunch* L);
+// The kernel variant linear_wave_prepare picks for a wave-engine choice `c`. has_mom: a momentum
+// buffer exists; stamps: phase timers requested. Host only, needs no device (the bindings' query).
+int linear_wave_variant(const FusedMlpArgs& a, const PersistArgs& p, const PersistChoice& c, bool has_mom, bool stamps);
 hipError_t mlp_tp_prepare(PersistLaunch* L);
 hipError_t fused_mlp_workgroup_prepare(PersistLaunch* L);
 size_t fused_mlp_persistent_lds_bytes(int B, int Din, int H, int Dout, int num_samples, int world);

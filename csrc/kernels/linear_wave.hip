@@ -1,11 +1,12 @@
 // Host dispatch of the single-wave persistent engine (linear_wave_impl.h).
 #include <algorithm>
+#include <cstdlib>
 #include "common.h"
 #include "kernels.h"
 
 namespace ptdt {
 
-#define PTDT_LW_DECL(tag) const void* linear_wave_pick_##tag(int L, int R, int kp, int dout);
+#define PTDT_LW_DECL(tag) const void* linear_wave_pick_##tag(int L, int R, int kp, int dout, int var);
 PTDT_LW_DECL(ce_soft) PTDT_LW_DECL(ce_soft_ar) PTDT_LW_DECL(ce_index) PTDT_LW_DECL(ce_index_ar)
 PTDT_LW_DECL(mse) PTDT_LW_DECL(mse_ar)
 #undef PTDT_LW_DECL
@@ -24,12 +25,18 @@ size_t ring_bytes(const FusedMlpArgs& a, const PersistArgs& p) {
   return (size_t)(2 * S + kWavePrefetch) * 64 * sizeof(float);
 }
 
-const void* pick(int loss, bool ar, int L, int R, int kp, int dout) {
+// var: WaveKernelVariant (lean variants exist for layout F only; nullptr otherwise)
+const void* pick(int loss, bool ar, int L, int R, int kp, int dout, int var = kWaveGeneric) {
   switch (loss) {
-    case kLossCEIndex: return ar ? linear_wave_pick_ce_index_ar(L, R, kp, dout) : linear_wave_pick_ce_index(L, R, kp, dout);
-    case kLossMSE: return ar ? linear_wave_pick_mse_ar(L, R, kp, dout) : linear_wave_pick_mse(L, R, kp, dout);
-    default: return ar ? linear_wave_pick_ce_soft_ar(L, R, kp, dout) : linear_wave_pick_ce_soft(L, R, kp, dout);
+    case kLossCEIndex:
+      return ar ? linear_wave_pick_ce_index_ar(L, R, kp, dout, var) : linear_wave_pick_ce_index(L, R, kp, dout, var);
+    case kLossMSE: return ar ? linear_wave_pick_mse_ar(L, R, kp, dout, var) : linear_wave_pick_mse(L, R, kp, dout, var);
+    default: return ar ? linear_wave_pick_ce_soft_ar(L, R, kp, dout, var) : linear_wave_pick_ce_soft(L, R, kp, dout, var);
   }
+}
+// layout F reduces the losses in the helper waves when the ring fits next to the lists
+bool ring_fits(const FusedMlpArgs& a, const PersistArgs& p, const PersistChoice& c) {
+  return c.L == 0 && lds_bytes(a, p) + ring_bytes(a, p) + kStaticLds <= 160 * 1024;
 }
 
 int log2i(int v) {
@@ -106,16 +113,32 @@ bool linear_wave_choose(const FusedMlpArgs& a, const PersistArgs& p, PersistChoi
   return best_cost < 1e30;
 }
 
+// A lean variant is picked only when the plan proves what it leaves out dead: layout F with the loss
+// ring, every batch full with B == 16 R rows (no row masks, one loss scale), plain SGD or momentum
+// without weight decay, no stamps. Everything a relaunch can change (persist_set_position: step count
+// and start position; the timeline address) stays a run-time value in every variant.
+// PTDT_WAVE_GENERIC=1 forces the generic kernel (A/B runs, the bitwise tests).
+int linear_wave_variant(const FusedMlpArgs& a, const PersistArgs& p, const PersistChoice& c, bool has_mom, bool stamps) {
+  const char* env = std::getenv("PTDT_WAVE_GENERIC");
+  if (env != nullptr && env[0] != '\0' && env[0] != '0') return kWaveGeneric;
+  if (c.engine != kEngWave || !ring_fits(a, p, c) || stamps) return kWaveGeneric;
+  if (a.B != 16 * c.R || p.num_samples % a.B != 0 || a.weight_decay != 0.f) return kWaveGeneric;
+  return has_mom && a.momentum != 0.f ? kWaveLeanMom : kWaveLeanPlain;
+}
+
 hipError_t linear_wave_prepare(PersistLaunch* L) {
   const FusedMlpArgs& a = L->a;
   const PersistChoice& c = L->choice;
   size_t lds = lds_bytes(a, L->p);
   L->p.loss_ring = 0;
-  if (c.L == 0 && lds + ring_bytes(a, L->p) + kStaticLds <= 160 * 1024) {
+  if (ring_fits(a, L->p, c)) {
     L->p.loss_ring = 1;
     lds += ring_bytes(a, L->p);
   }
-  return persist_set_kernel(L, pick(a.loss_kind, a.ar.world > 1, c.L, c.R, c.kp, a.Dout), kThreads, lds);
+  const bool ar = a.ar.world > 1;
+  L->kernel_variant = linear_wave_variant(a, L->p, c, a.mom != nullptr, L->p.stamps != nullptr);
+  if (pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant) == nullptr) L->kernel_variant = kWaveGeneric;
+  return persist_set_kernel(L, pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant), kThreads, lds);
 }
 
 }  // namespace ptdt

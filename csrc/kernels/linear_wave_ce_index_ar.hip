@@ -4,7 +4,7 @@
 #include "linear_wave_impl.h"
 
 namespace ptdt {
-const void* linear_wave_pick_ce_index_ar(int L, int R, int kp, int dout) {
-  return lw::pick<kLossCEIndex, true>(L, R, kp, dout);
+const void* linear_wave_pick_ce_index_ar(int L, int R, int kp, int dout, int var) {
+  return lw::pick<kLossCEIndex, true>(L, R, kp, dout, var);
 }
 }  // namespace ptdt

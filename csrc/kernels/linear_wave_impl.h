@@ -1061,9 +1061,16 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
   if constexpr ((KP & 1) != 0) x[KP - 1] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off + 4 * (KP - 1), 0, 0));
 }
 
-template <int R, int KP, int DOUT, int LOSS, bool AR>
+// VAR (WaveKernelVariant, chosen per plan by linear_wave_variant): the generic kernel decides the SGD
+// kind, the loss path, the row masks and the stamps at run time. A lean variant (kWaveLeanPlain /
+// kWaveLeanMom) is the same kernel with the plan's facts as constants -- that SGD kind, the loss ring
+// on, every batch full with B == 16 R rows, no stamps -- so the code a plan never runs is not in the
+// object (one step loop instead of five). Barriers, LDS layout, list handling, prefetch depth and
+// every floating-point operation and its order are the generic kernel's: the results are its bits.
+template <int R, int KP, int DOUT, int LOSS, bool AR, int VAR = kWaveGeneric>
 __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a, PersistArgs pa) {
   static_assert(R == 1 || R == 2 || R == 4, "rows per lane: 1, 2 or 4");
+  constexpr bool LEAN = VAR != kWaveGeneric;
   // DOUT == 1: reduce-scatter, one row per lane (rows q & (R-1)); else every lane all rows
   constexpr bool SCATTER = DOUT == 1 && R > 1;
   constexpr int RY = SCATTER ? 1 : R;  // target rows a lane loads / computes the loss of
@@ -1073,18 +1080,35 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // the branch it fed (stamps, timeline, start position, momentum, ...): five dependent kernel-
   // argument round trips before the first list load, and the start position came through a flat
   // load of a pointer selected between the cursor and the argument (round-5 kernel-entry asm).
+  // (A second batch with what the trainer needs between the barrier and its loop -- step count,
+  // dataset rows, targets, optimizer scalars, the counters -- measured no gain: profiles/wave_variants.md.)
   const int64_t r_now = (int64_t)__builtin_amdgcn_s_memrealtime();
-  int64_t* const stamps_p = pa.stamps;
+  int64_t* const stamps_p = LEAN ? nullptr : pa.stamps;  // a plan with stamps runs the generic kernel
   int64_t* const tl_p = pa.tl;
-  const int B = a.B, Din = a.Din, ns_arg = pa.num_samples, has_start = pa.has_start, start_e = pa.start_e,
+  const int B = LEAN ? 16 * R : a.B;  // lean: every batch fills the 16 R row slots
+  const int Din = a.Din, ns_arg = pa.num_samples, has_start = pa.has_start, start_e = pa.start_e,
             start_j = pa.start_j, has_bias_arg = a.has_bias, ldx_arg = a.ldx;
   const int32_t* const cursor_p = pa.cursor;
   const float* const P_arg = a.P;
   const float* const mom_arg = a.mom;
   const float* const X_arg = a.X;
   const float momentum_arg = a.momentum;
-  asm volatile("" ::"s"(stamps_p), "s"(tl_p), "s"(B), "s"(Din), "s"(ns_arg), "s"(has_start), "s"(start_e), "s"(start_j),
-               "s"(has_bias_arg), "s"(ldx_arg), "s"(cursor_p), "s"(P_arg), "s"(mom_arg), "s"(X_arg), "s"(momentum_arg));
+  if constexpr (!LEAN) {
+    asm volatile("" ::"s"(stamps_p), "s"(tl_p), "s"(B), "s"(Din), "s"(ns_arg), "s"(has_start), "s"(start_e), "s"(start_j),
+                 "s"(has_bias_arg), "s"(ldx_arg), "s"(cursor_p), "s"(P_arg), "s"(mom_arg), "s"(X_arg), "s"(momentum_arg));
+  } else {
+    asm volatile("" ::"s"(tl_p), "s"(Din), "s"(ns_arg), "s"(has_start), "s"(start_e), "s"(start_j), "s"(has_bias_arg),
+                 "s"(ldx_arg), "s"(cursor_p), "s"(P_arg), "s"(X_arg));
+    if constexpr (VAR == kWaveLeanMom) asm volatile("" ::"s"(mom_arg), "s"(momentum_arg));
+  }
+  const int n = pa.n_steps, n_rows_arg = pa.N, loss_ring_arg = pa.loss_ring, nesterov = a.nesterov,
+            ignore_index_arg = a.ignore_index;
+  const void* const Y_arg = LOSS == kLossCEIndex ? (const void*)a.Yi : (const void*)a.Yf;
+  const float grad_scale_arg = a.grad_scale, lr = a.lr, damp = a.dampening, wd = a.weight_decay;
+  int32_t* const opt_step_p = a.opt_step;
+  float* const losses_p = pa.losses;
+  uint32_t* const seq_p = AR ? a.ar.seq : nullptr;
+  int* const err_p = AR ? a.ar.err : nullptr;
   // diagnostic (stamps): kernel entry, for the prologue share of a launch (stamps[10], 10 ns ticks)
   const int64_t r_entry = stamps_p != nullptr ? r_now : 0;
   if (tl_p != nullptr && threadIdx.x == 0)  // tl_mark(tl, 0) with the entry time taken above
@@ -1101,7 +1125,6 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     j0 = cursor_p[1];
   }
   const int64_t pos0 = (int64_t)e0 * S + j0;
-  const int n = pa.n_steps;
   const int T = (j0 + n - 1) / S;  // epoch barriers crossed (j0 < S)
   auto list = [&](int e) { return elist + (e & 1) * estride; };
   // diagnostic prologue split (stamps[11..13], 10 ns ticks): position known, list in LDS, after the barrier
@@ -1127,7 +1150,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   const int q = (lane & 63) >> 4, i = lane & 15;  // feature group, row slot
   const int k0 = q * KP;
   const bool hb = has_bias_arg != 0;
-  const bool use_mom = mom_arg != nullptr && momentum_arg != 0.f;
+  const bool use_mom = VAR == kWaveLeanMom || (VAR == kWaveGeneric && mom_arg != nullptr && momentum_arg != 0.f);
   const int nW = DOUT * Din;
   float W[DOUT][KP], M[DOUT][KP], Wb[DOUT], Mb[DOUT];
   if (wave == 0) {
@@ -1149,17 +1172,17 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   const int ldx = ldx_arg > 0 ? ldx_arg : Din;  // feature slots past Din read X's zero padding
   // Gathers through buffer resources with 32-bit byte offsets (the host checks N * ldx * 4 < 2^31,
   // sel, ldx * 4 < 2^24): one v_mad_u32_u24 per row instead of a 64-bit address chain.
-  const uint32_t n_rows = (uint32_t)pa.N;
+  const uint32_t n_rows = (uint32_t)n_rows_arg;
   const __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(X_arg, n_rows * (uint32_t)ldx * 4u);
-  const __amdgpu_buffer_rsrc_t yrs =
-      LOSS == kLossCEIndex ? buffer_rsrc(a.Yi, n_rows * 8u) : buffer_rsrc(a.Yf, n_rows * (uint32_t)(DOUT * 4));
+  const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(Y_arg, n_rows * (LOSS == kLossCEIndex ? 8u : (uint32_t)(DOUT * 4)));
   const uint32_t ldx4 = (uint32_t)ldx * 4u, k04 = (uint32_t)k0 * 4u;
   // loss scales of a full batch and of the one short last batch (nb_last == B if none); each batch
-  // carries its pair, selected at fetch time (off the step's dependent chain)
-  const int nb_last = ns_arg - (S - 1) * B;
+  // carries its pair, selected at fetch time (off the step's dependent chain). Lean: no short batch,
+  // the selects and the row masks (`valid`) fold away.
+  const int nb_last = LEAN ? B : ns_arg - (S - 1) * B;
   const float inv_full = 1.f / (float)((LOSS == kLossMSE) ? B * DOUT : B);
   const float inv_last = 1.f / (float)((LOSS == kLossMSE) ? nb_last * DOUT : nb_last);
-  const float gs_full = a.grad_scale * inv_full, gs_last = a.grad_scale * inv_last;
+  const float gs_full = grad_scale_arg * inv_full, gs_last = grad_scale_arg * inv_last;
   auto load_batch = [&](Batch<R, KP, DOUT, RY>& f, const int (&sel)[R], int sel_y, int nb) {
     f.nb = nb;
     f.cg = nb == B ? gs_full : gs_last;
@@ -1188,12 +1211,14 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // Loss ring (pa.loss_ring): the trainer stores each lane's scaled loss share
   // per step (one ds_write), the helper waves add the 64 shares and write
   // losses[] -- the per-step cross-lane loss reduction leaves the critical path.
-  const int ring = pa.loss_ring ? 2 * S + kNB : 0;  // slots; 2 epochs + prefetch depth never overwrite unread
+  const int ring = (LEAN || loss_ring_arg) ? 2 * S + kNB : 0;  // slots; 2 epochs + prefetch depth never overwrite unread
   float* const lring = reinterpret_cast<float*>(elist + 2 * estride + 16);  // after the 8 u64 timer slots
   __syncthreads();
   pstamp(2);
-  tl_mark(pa.tl, 1);
-  if (wave != 0) {
+  tl_mark(tl_p, 1);
+  // lean: the helper waves' code is laid out behind the trainer's (entry, list copy, barrier, setup,
+  // loop, write-back run contiguously: the instruction cache is cold at every launch)
+  if (LEAN ? __builtin_expect(wave != 0, 0) : (long)(wave != 0)) {
     const int ht = (int)threadIdx.x - 64, hn = kThreads - 64;
     int64_t lo = pos0;
     // positions [lo, hi): 16 lanes per position (a DPP row), 4 shares per lane (one 16-B LDS read),
@@ -1221,19 +1246,17 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         rank_epoch_indices_or(given_list(pa, e0 + i + 1), list(e0 + i + 1), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples, pa.seed, e0 + i + 1,
                            pa.shuffle, ht, hn, lc);
       // at barrier i the trainer has trained every position before (e0+i)*S - kNB
-      if (ring) reduce_losses(min((int64_t)(e0 + i) * S - kNB, pos0 + n));
+      if (LEAN || ring) reduce_losses(min((int64_t)(e0 + i) * S - kNB, pos0 + n));
     }
-    if (ring) {
+    if (LEAN || ring) {
       __syncthreads();  // the trainer's final barrier: every step done
       reduce_losses(pos0 + n);
     }
     return;
   }
 
-  const float lr = a.lr, mu = a.momentum, damp = a.dampening, wd = a.weight_decay;
-  const int nesterov = a.nesterov;
-
-  int opt_step = a.opt_step ? *a.opt_step : 0;
+  const float mu = momentum_arg;
+  int opt_step = opt_step_p != nullptr ? *opt_step_p : 0;
   const XgmiArgs& ar = a.ar;
   const int world = AR ? ar.world : 1;
   uint64_t PTDT_GLOBAL* push_dst = nullptr;  // row slot i pushes to rank i
@@ -1242,9 +1265,9 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     if (i == r && r < world) push_dst = (uint64_t PTDT_GLOBAL*)ar.peers[r];
   uint64_t PTDT_GLOBAL* const poll_src = (uint64_t PTDT_GLOBAL*)ar.local;
   const int my_rank = ar.rank, max_elems = ar.max_elems;
-  float PTDT_GLOBAL* const losses = gptr_w(pa.losses);
-  uint32_t seq = AR ? *ar.seq : 0u;
-  bool failed = AR && *ar.err != 0;
+  float PTDT_GLOBAL* const losses = gptr_w(losses_p);
+  uint32_t seq = AR ? *seq_p : 0u;
+  bool failed = AR && *err_p != 0;  // a peer already timed out earlier: do not wait again
   const float inv_w = 1.f / (float)world;
   // world 2: one packed store + one poll per step (ll_exchange_pair), staged through 128 LDS floats
   __shared__ float xpair[AR ? 128 : 1];
@@ -1282,7 +1305,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   };
 
   Ticks tk;
-  tk.on = pa.stamps != nullptr;
+  tk.on = stamps_p != nullptr;
   tk.acc = reinterpret_cast<unsigned long long*>(elist + 2 * estride);
   if (tk.on && lane == 0)
     for (int k = 0; k < 8; ++k) tk.acc[k] = 0ull;
@@ -1305,7 +1328,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         l = -y[0] * ls0;
         g[0] = fmaf(ls0, y[0], 0.f);  // exp(ls0) y - y: the same bits (+0, or NaN), one op shorter
       } else {
-        const bool use = yi != a.ignore_index;
+        const bool use = yi != ignore_index_arg;
         g[0] = use ? (ls0 + 1.f) - (yi == 0 ? 1.f : 0.f) : 0.f;
         l = use ? -(yi == 0 ? ls0 : 0.f) : 0.f;
         cnt = use ? 1.f : 0.f;
@@ -1328,7 +1351,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
 #pragma unroll
         for (int c = 0; c < DOUT; ++c) g[c] = __expf(z[c] - lse) * tsum - y[c];
       } else {
-        const bool use = yi != a.ignore_index;
+        const bool use = yi != ignore_index_arg;
         float zy = 0.f;
 #pragma unroll
         for (int c = 0; c < DOUT; ++c) {
@@ -1381,7 +1404,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
       z += Wb[0];
       float gz, l, cnt;
-      row_loss(&z, f.y[0], f.yi[0], rho_own * 16 + i < nb, &gz, l, cnt);
+      row_loss(&z, f.y[0], f.yi[0], LEAN || rho_own * 16 + i < nb, &gz, l, cnt);
       // each batch row counted once: R == 2 has every row in two DPP rows
       const bool owner = R == 4 || q < 2;
       lsum = owner ? l : 0.f;
@@ -1409,7 +1432,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
 #pragma unroll
         for (int c = 0; c < DOUT; ++c) z[c] = allrows(zp[rho][c]) + Wb[c];
         float l, cnt;
-        row_loss(z, f.y[rho], f.yi[rho], rho * 16 + i < nb, g[rho], l, cnt);
+        row_loss(z, f.y[rho], f.yi[rho], LEAN || rho * 16 + i < nb, g[rho], l, cnt);
         lsum += l;
         csum += cnt;
       }
@@ -1426,7 +1449,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       inv_denom = f.cl;
     }
     // SCATTER already applied the scale to dL/dz before the all-gather
-    const float coef = (SCATTER && LOSS != kLossCEIndex) ? 1.f : a.grad_scale * inv_denom;
+    const float coef = (SCATTER && LOSS != kLossCEIndex) ? 1.f : grad_scale_arg * inv_denom;
     tk.tick(2);
     // ---- backward: column sums over the 16 row slots of this DPP row
     float gW[DOUT][KP], gb[DOUT];
@@ -1578,7 +1601,11 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   using Plain = std::integral_constant<int, kSgdPlain>;
   using NoMom = std::integral_constant<int, kSgdNoMom>;
   using Mom = std::integral_constant<int, kSgdMom>;
-  if (use_mom) {
+  if constexpr (VAR == kWaveLeanPlain) {  // the plan's loop is the only one in a lean kernel
+    run(Plain{}, std::true_type{});
+  } else if constexpr (VAR == kWaveLeanMom) {
+    run(Mom{}, std::true_type{});
+  } else if (use_mom) {
     if (ring) run(Mom{}, std::true_type{});
     else run(Mom{}, std::false_type{});
   } else if (ring) {
@@ -1587,7 +1614,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   } else {
     run(NoMom{}, std::false_type{});
   }
-  tl_mark(pa.tl, 2);
+  tl_mark(tl_p, 2);
   // final stores first, then the remaining barriers: their latency overlaps the helpers' tail
   if (i == 0) {
     const auto Pw = gptr_w(a.P);
@@ -1613,8 +1640,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     const int64_t pos = pos0 + done;
     pa.cursor[0] = (int)(pos / S);
     pa.cursor[1] = (int)(pos % S);
-    if (a.opt_step) *a.opt_step = opt_step;
-    if (AR) *ar.seq = seq;
+    if (opt_step_p != nullptr) *opt_step_p = opt_step;
+    if (AR) *seq_p = seq;
     if (tk.on) {
       for (int k = 0; k < 6; ++k) pa.stamps[k] += (int64_t)tk.acc[k];
       pa.stamps[7] += (int64_t)__builtin_amdgcn_s_memtime() - t_begin;
@@ -1631,10 +1658,10 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     __syncthreads();
     ++barriers;
   }
-  if (ring) __syncthreads();  // final barrier: the helpers reduce the remaining losses
-  if (pa.tl != nullptr) {
+  if (LEAN || ring) __syncthreads();  // final barrier: the helpers reduce the remaining losses
+  if (tl_p != nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the final stores issued above are done
-    tl_mark(pa.tl, 3);
+    tl_mark(tl_p, 3);
   }
 }
 
@@ -1642,10 +1669,16 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
 // combinations whose register footprint fits (no scratch). nullptr otherwise.
 // Keep in sync with kWaveConfigs in linear_wave.hip.
 // L == 0 selects layout F (linear_wave_f_kernel), R in {1, 2, 4}.
+// var: WaveKernelVariant. The lean variants exist for layout F only (every F configuration x
+// {plain, momentum}); the row-group layouts have the generic kernel alone.
 template <int LOSS, bool AR>
-const void* pick(int L, int R, int kp, int dout) {
-#define PTDT_LWF(RR, KP, DO) \
-  if (L == 0 && R == RR && kp == KP && dout == DO) return (const void*)linear_wave_f_kernel<RR, KP, DO, LOSS, AR>;
+const void* pick(int L, int R, int kp, int dout, int var) {
+  if (var != kWaveGeneric && L != 0) return nullptr;
+#define PTDT_LWF(RR, KP, DO)                                                                                \
+  if (L == 0 && R == RR && kp == KP && dout == DO)                                                          \
+    return var == kWaveLeanPlain ? (const void*)linear_wave_f_kernel<RR, KP, DO, LOSS, AR, kWaveLeanPlain>  \
+           : var == kWaveLeanMom ? (const void*)linear_wave_f_kernel<RR, KP, DO, LOSS, AR, kWaveLeanMom>    \
+                                 : (const void*)linear_wave_f_kernel<RR, KP, DO, LOSS, AR>;
 #define PTDT_LWF_R(RR)                                                                             \
   PTDT_LWF(RR, 4, 1) PTDT_LWF(RR, 5, 1) PTDT_LWF(RR, 8, 1) PTDT_LWF(RR, 10, 1) PTDT_LWF(RR, 16, 1) \
   PTDT_LWF(RR, 4, 2) PTDT_LWF(RR, 5, 2) PTDT_LWF(RR, 8, 2)
