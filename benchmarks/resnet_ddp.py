@@ -64,6 +64,10 @@ def main(argv=None):
     ap.add_argument("--sync_bn", action="store_true",
                     help="cross-rank BatchNorm statistics: ops.norm.SyncBatchNorm (native) or torch.nn.SyncBatchNorm "
                          "(--impl torch); PTDT_SYNCBN_FORCE=1 takes the synchronised path on one GPU too")
+    ap.add_argument("--clip_grad_norm", type=float, default=None,
+                    help="clip the gradient 2-norm to this value between backward and step: ops.clip.GradClipper "
+                         "fused into FusedSGD (native; captured with the step) or torch.nn.utils.clip_grad_norm_ "
+                         "(--impl torch). Default: off")
     a = ap.parse_args(argv)
     torch.backends.cudnn.benchmark = not a.no_cudnn_benchmark and not a.deterministic
     torch.backends.cudnn.deterministic = a.deterministic
@@ -100,6 +104,11 @@ def main(argv=None):
 
         ddp = TorchDDP(model, device_ids=[dev.index], bucket_cap_mb=a.bucket_cap_mb or 25)
         opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
+    clipper, grad_norm = None, None
+    if a.clip_grad_norm is not None and a.impl == "native":
+        from pytorch_distributed_training_tutorials_amd.ops.clip import GradClipper
+
+        clipper = GradClipper(list(model.parameters()), a.clip_grad_norm, optimizer=opt)  # created once
     x = torch.empty(a.batch_size, 3, a.image, a.image, device=dev)
     native().philox_(x, 1234 + rank, 0, 1)
     if not a.no_channels_last:
@@ -120,6 +129,7 @@ def main(argv=None):
     from pytorch_distributed_training_tutorials_amd.utils.graphs import GraphedStep
 
     def step():
+        nonlocal grad_norm
         if a.impl == "native":
             ddp.zero_grad()
         else:
@@ -129,6 +139,10 @@ def main(argv=None):
             out = ddp(x)
         loss = cross_entropy(out.float(), y)
         loss.backward()
+        if clipper is not None:
+            clipper()  # device record only: part of the captured step
+        elif a.clip_grad_norm is not None:
+            grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), a.clip_grad_norm, foreach=True)
         opt.step()
         if a.loss_curve and not torch.cuda.is_current_stream_capturing():
             curve.append(loss.detach().clone())
@@ -230,6 +244,9 @@ def main(argv=None):
             "buckets_MB": [round(b / 2 ** 20, 2) for b in ddp.bucket_sizes_bytes()] if a.impl == "native" else None,
             **({"loss_curve": [round(float(v), 4) for v in curve]} if a.loss_curve else {}),
             **({"graph": graph_info} if graph_info else {}),
+            **({"clip_grad_norm": a.clip_grad_norm,
+                "grad_norm": float(clipper.norm if clipper is not None else grad_norm)}
+               if a.clip_grad_norm is not None else {}),
             "final_loss": final, "finite": True, "kernel_choices": _choices(), "steps_total": executed + a.steps, **({"tag": a.tag} if a.tag else {}),
         }), flush=True)
     env.destroy_process_group()

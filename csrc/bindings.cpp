@@ -15,6 +15,7 @@
 
 #include "comm/rccl_comm.h"
 #include "comm/xgmi_comm.h"
+#include "kernels/chunks.h"
 #include "kernels/kernels.h"
 #include "reducer/reducer.h"
 
@@ -482,27 +483,37 @@ void torch_perm_py(Tensor seeds, int64_t n, int64_t W, int64_t rank, int64_t num
 }
 
 // ------------------------------------------------------------- optimizers
+// the optional clip coefficient of the optimizer steps: one f32 value on the parameters' device
+const float* gcoef_ptr(const c10::optional<Tensor>& gcoef, const Tensor& p) {
+  if (!gcoef.has_value() || !gcoef->defined()) return nullptr;
+  TORCH_CHECK(gcoef->is_cuda() && gcoef->device() == p.device() && gcoef->scalar_type() == at::kFloat &&
+                  gcoef->numel() == 1,
+              "gcoef must be one float32 value on the parameters' device");
+  return gcoef->data_ptr<float>();
+}
+
 void sgd_flat_(Tensor p, Tensor g, c10::optional<Tensor> mom, c10::optional<Tensor> step, double lr,
-               double momentum, double dampening, double wd, bool nesterov, double grad_scale) {
+               double momentum, double dampening, double wd, bool nesterov, double grad_scale,
+               c10::optional<Tensor> gcoef) {
   check_gpu(p, "param");
   check_gpu(g, "grad");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && p.numel() == g.numel());
   c10::hip::HIPGuard guard(p.device().index());
   hip_check(sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), ptr_or_null<float>(mom),
                      ptr_or_null<int32_t>(step), p.numel(), (float)lr, (float)momentum, (float)dampening,
-                     (float)wd, nesterov, (float)grad_scale, cur_stream(p)),
+                     (float)wd, nesterov, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p)),
             "sgd_flat");
 }
 
 void adam_flat_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, double lr, double b1, double b2,
-                double eps, double wd, bool decoupled, double grad_scale) {
+                double eps, double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef) {
   check_gpu(p, "param");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.numel() == p.numel() && m.numel() == p.numel() &&
               v.numel() == p.numel() && step.scalar_type() == at::kInt);
   c10::hip::HIPGuard guard(p.device().index());
   hip_check(adam_flat(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                       step.data_ptr<int32_t>(), p.numel(), (float)lr, (float)b1, (float)b2, (float)eps,
-                      (float)wd, decoupled, (float)grad_scale, cur_stream(p)),
+                      (float)wd, decoupled, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p)),
             "adam_flat");
 }
 
@@ -513,7 +524,7 @@ void for_tensor_chunks(size_t n, F&& f) {
 
 void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> moms,
                 c10::optional<Tensor> step, double lr, double momentum, double dampening, double wd,
-                bool nesterov, double grad_scale, std::vector<Tensor> shadows) {
+                bool nesterov, double grad_scale, std::vector<Tensor> shadows, c10::optional<Tensor> gcoef) {
   if (ps.empty()) return;
   TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
   TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat),
@@ -541,14 +552,14 @@ void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tens
       }
     }
     hip_check(sgd_multi(tl, dt, ptr_or_null<int32_t>(step), (float)lr, (float)momentum, (float)dampening,
-                        (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0])),
+                        (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0])),
               "sgd_multi");
   });
 }
 
 void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> ms,
                  std::vector<Tensor> vs, Tensor step, double lr, double b1, double b2, double eps,
-                 double wd, bool decoupled, double grad_scale) {
+                 double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef) {
   if (ps.empty()) return;
   TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
   const int dt = dt_of(ps[0]);
@@ -570,9 +581,69 @@ void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
       tl.s2[i - a] = vs[i].data_ptr<float>();
     }
     hip_check(adam_multi(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)b1, (float)b2, (float)eps,
-                         (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0])),
+                         (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0])),
               "adam_multi");
   });
+}
+
+// ------------------------------------------------------------- gradient clipping
+// spans: <= kMaxTensorsPerLaunch dense 1-D views of one dtype on one device (ops/clip.py plans them)
+SpanList span_list(const std::vector<Tensor>& spans, const char* what) {
+  TORCH_CHECK(!spans.empty() && spans.size() <= (size_t)kMaxTensorsPerLaunch, what, ": 1..", kMaxTensorsPerLaunch,
+              " spans per launch");
+  SpanList sl{};
+  sl.n = (int)spans.size();
+  for (size_t i = 0; i < spans.size(); ++i) {
+    const Tensor& t = spans[i];
+    TORCH_CHECK(t.is_cuda() && t.is_non_overlapping_and_dense(), what, ": spans must be dense GPU tensors");
+    TORCH_CHECK(t.device() == spans[0].device() && t.scalar_type() == spans[0].scalar_type(), what,
+                ": one device and one dtype per launch");
+    sl.numel[i] = t.numel();
+    sl.p[i] = t.data_ptr();
+  }
+  return sl;
+}
+
+void check_clip_rec(const Tensor& rec, const Tensor& like, const char* what) {
+  TORCH_CHECK(rec.is_cuda() && rec.device() == like.device() && rec.scalar_type() == at::kFloat &&
+                  rec.is_contiguous() && rec.numel() >= 2,
+              what, ": rec must be float32[2] on the gradients' device");
+}
+
+// ws[first_slot + b] = partial of chunk b of the spans; returns the number of slots written
+int64_t clip_norm_partials_(std::vector<Tensor> spans, Tensor ws, int64_t first_slot, int64_t norm) {
+  const SpanList sl = span_list(spans, "clip_norm_partials_");
+  const int64_t nb = chunk_blocks(sl);
+  TORCH_CHECK(ws.is_cuda() && ws.device() == spans[0].device() && ws.scalar_type() == at::kFloat &&
+                  ws.is_contiguous() && first_slot >= 0 && first_slot + nb <= ws.numel(),
+              "clip_norm_partials_: ws must be float32 on the gradients' device with first_slot + chunks slots");
+  c10::hip::HIPGuard guard(ws.device().index());
+  hip_check(clip_norm_partials(sl, dt_of(spans[0]), (int)norm, ws.data_ptr<float>(), first_slot, cur_stream(ws)),
+            "clip_norm_partials");
+  return nb;
+}
+
+void clip_norm_finalize_(Tensor ws, int64_t n, int64_t norm, double max_norm, bool partial, Tensor rec) {
+  check_clip_rec(rec, ws, "clip_norm_finalize_");
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat && ws.is_contiguous() && n >= 0 && n <= ws.numel(),
+              "clip_norm_finalize_: ws must hold n float32 slots");
+  c10::hip::HIPGuard guard(ws.device().index());
+  hip_check(clip_norm_finalize(ws.data_ptr<float>(), n, (int)norm, (float)max_norm, partial ? 1 : 0,
+                               rec.data_ptr<float>(), cur_stream(ws)),
+            "clip_norm_finalize");
+}
+
+void clip_scale_(std::vector<Tensor> spans, Tensor rec) {
+  const SpanList sl = span_list(spans, "clip_scale_");
+  check_clip_rec(rec, spans[0], "clip_scale_");
+  c10::hip::HIPGuard guard(rec.device().index());
+  hip_check(clip_scale(sl, dt_of(spans[0]), rec.data_ptr<float>(), cur_stream(rec)), "clip_scale");
+}
+
+void clip_clamp_(std::vector<Tensor> spans, double c) {
+  const SpanList sl = span_list(spans, "clip_clamp_");
+  c10::hip::HIPGuard guard(spans[0].device().index());
+  hip_check(clip_clamp(sl, dt_of(spans[0]), (float)c, cur_stream(spans[0])), "clip_clamp");
 }
 
 void bucket_copy(std::vector<Tensor> ts, Tensor flat, double scale, bool unpack) {
@@ -1770,12 +1841,25 @@ PYBIND11_MODULE(_C, m) {
         py::arg("has_bias") = true, py::arg("momentum") = 0.0, py::arg("weight_decay") = 0.0,
         py::arg("stamps") = false);
   m.def("fused_mlp_lds_bytes", [](int B, int Din, int H, int Dout) { return fused_mlp_lds_bytes(B, Din, H, Dout); });
-  m.def("sgd_flat_", &sgd_flat_);
-  m.def("adam_flat_", &adam_flat_);
+  // gcoef (optional, last): a device float multiplied into the gradient scale, the clip coefficient
+  m.def("sgd_flat_", &sgd_flat_, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("step"), py::arg("lr"),
+        py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),
+        py::arg("gcoef") = py::none());
+  m.def("adam_flat_", &adam_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("decoupled"),
+        py::arg("grad_scale"), py::arg("gcoef") = py::none());
   m.def("sgd_multi_", &sgd_multi_, py::arg("ps"), py::arg("gs"), py::arg("moms"), py::arg("step"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),
-        py::arg("shadows") = std::vector<Tensor>{});
-  m.def("adam_multi_", &adam_multi_);
+        py::arg("shadows") = std::vector<Tensor>{}, py::arg("gcoef") = py::none());
+  m.def("adam_multi_", &adam_multi_, py::arg("ps"), py::arg("gs"), py::arg("ms"), py::arg("vs"), py::arg("step"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("decoupled"),
+        py::arg("grad_scale"), py::arg("gcoef") = py::none());
+  m.def("clip_norm_partials_", &clip_norm_partials_, py::arg("spans"), py::arg("ws"), py::arg("first_slot"),
+        py::arg("norm"), "per-chunk norm partials (norm 0: sum of squares, 1: max |g|); returns the slot count");
+  m.def("clip_norm_finalize_", &clip_norm_finalize_, py::arg("ws"), py::arg("n"), py::arg("norm"), py::arg("max_norm"),
+        py::arg("partial"), py::arg("rec"), "rec = {total_norm, clip_coef} from n partial slots");
+  m.def("clip_scale_", &clip_scale_, py::arg("spans"), py::arg("rec"), "spans *= rec[1] (skipped when exactly 1)");
+  m.def("clip_clamp_", &clip_clamp_, py::arg("spans"), py::arg("c"), "spans = clamp(spans, -c, c), NaN kept");
   m.def("bucket_copy", &bucket_copy);
   m.def("scale_", &scale_);
   m.def("cast_multi_", &cast_multi_, py::arg("dsts"), py::arg("srcs"));

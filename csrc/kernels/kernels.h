@@ -237,13 +237,15 @@ size_t torch_perm_lds_bytes(int n);
 // Optimizers on flat buffers and multi-tensor lists (csrc/kernels/optim.hip).
 // torch.optim.SGD semantics: d = g + wd*p; buf = (first ? d : mu*buf + (1-damp)*d);
 // d = nesterov ? d + mu*buf : buf; p -= lr*d.
+// gcoef (all four): optional device float the kernel multiplies into grad_scale when it starts --
+// the gradient-clipping coefficient of gradclip.hip, applied without rewriting the gradients.
 hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
                     float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s);
+                    float grad_scale, hipStream_t s, const float* gcoef = nullptr);
 // Adam/AdamW; step is a device counter already incremented for this step.
 hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
                      float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s);
+                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef = nullptr);
 
 constexpr int kMaxTensorsPerLaunch = 32;
 struct TensorList {
@@ -257,10 +259,10 @@ struct TensorList {
 };
 hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
                      float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s);
+                     hipStream_t s, const float* gcoef = nullptr);
 hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s);
+                      hipStream_t s, const float* gcoef = nullptr);
 // dst[i] = src_i * scale over a list (bucket pack) or the reverse (unpack).
 struct CopyList {
   int n;
@@ -273,6 +275,32 @@ hipError_t bucket_unpack(const CopyList& cl, const void* flat, int dtype, float 
 hipError_t scale_inplace(void* x, int64_t n, int dtype, float scale, hipStream_t s);
 // tl.p[t] (f32) = tl.g[t] (bf16) elementwise, every tensor dense with matching layouts
 hipError_t cast_bf16_f32_multi(const TensorList& tl, hipStream_t s);
+
+// --------------------------------------------------------------------------
+// Gradient clipping (csrc/kernels/gradclip.hip). Capturable and deterministic: no atomics,
+// no memsets, no host reads. Gradients arrive as a list of dense spans of one dtype; block b
+// of a launch owns one kChunk-element chunk of one span (the optimizers' block mapping).
+struct SpanList {
+  int n;                                   // spans in this launch
+  int64_t numel[kMaxTensorsPerLaunch];
+  void* p[kMaxTensorsPerLaunch];
+};
+enum ClipNorm : int { kClipNorm2 = 0, kClipNormInf = 1 };
+// ws[first_slot + b] = the value of block b's chunk: its sum of squares (kClipNorm2) or its
+// max |g| (kClipNormInf, NaN propagates). Every slot has one writer, so ws needs no zeroing.
+hipError_t clip_norm_partials(const SpanList& sl, int dtype, int norm, float* ws, int64_t first_slot,
+                              hipStream_t s);
+// One workgroup combines ws[0, n) in a fixed order (float64 sum / max). partial == 0:
+// rec[0] = total_norm (sqrt of the sum, or the max), rec[1] = clip_coef =
+// min(1, max_norm / (total_norm + 1e-6)) (NaN stays NaN). partial == 1: rec[0] = the combined
+// value itself (no sqrt), rec[1] = 1 -- one device's share, which the caller copies into a
+// further slot of the first device's ws before that device finalises.
+hipError_t clip_norm_finalize(const float* ws, int64_t n, int norm, float max_norm, int partial, float* rec,
+                              hipStream_t s);
+// g *= rec[1] over the spans; blocks return without touching memory when rec[1] == 1.0f.
+hipError_t clip_scale(const SpanList& sl, int dtype, const float* rec, hipStream_t s);
+// g = min(max(g, -c), c), NaN kept (torch.clamp).
+hipError_t clip_clamp(const SpanList& sl, int dtype, float c, hipStream_t s);
 
 // --------------------------------------------------------------------------
 // Losses (csrc/kernels/loss.hip). Row-wise log-softmax CE (soft or index

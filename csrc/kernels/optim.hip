@@ -13,6 +13,7 @@
 //    to (tensor, chunk) by a prefix search over chunk counts.
 #include <type_traits>
 
+#include "chunks.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -20,7 +21,6 @@ namespace ptdt {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kChunk = 4096;  // elements per block in multi-tensor launches
 
 struct SgdHyper {
   float lr, mu, damp, wd, gscale;
@@ -62,7 +62,9 @@ __device__ __forceinline__ float adam_update(float p, float g, float* m, float* 
 
 __global__ void __launch_bounds__(kBlock) sgd_flat_kernel(float* __restrict__ p,
                                                           const float* __restrict__ g, float* mom,
-                                                          int32_t* step, int64_t n, SgdHyper h) {
+                                                          int32_t* step, int64_t n, SgdHyper h,
+                                                          const float* gcoef) {
+  if (gcoef != nullptr) h.gscale *= *gcoef;
   const bool first = step ? (*step == 0) : false;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t t0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -88,7 +90,8 @@ __global__ void sgd_step_inc(int32_t* step) { *step += 1; }
 __global__ void __launch_bounds__(kBlock) adam_flat_kernel(float* __restrict__ p,
                                                            const float* __restrict__ g, float* m,
                                                            float* v, const int32_t* step, int64_t n,
-                                                           AdamHyper h) {
+                                                           AdamHyper h, const float* gcoef) {
+  if (gcoef != nullptr) h.gscale *= *gcoef;
   const float t = (float)(*step);
   const float bc1 = 1.f - powf(h.b1, t);
   const float bc2s = sqrtf(1.f - powf(h.b2, t));
@@ -98,20 +101,10 @@ __global__ void __launch_bounds__(kBlock) adam_flat_kernel(float* __restrict__ p
 }
 
 // ---------------------------------------------------------------- multi-tensor
-__device__ __forceinline__ void locate_chunk(const int64_t* numel, int n, int blk, int& t,
-                                             int64_t& start) {
-  int acc = 0;
-  for (t = 0; t < n; ++t) {
-    const int c = (int)((numel[t] + kChunk - 1) / kChunk);
-    if (blk < acc + c) break;
-    acc += c;
-  }
-  start = (int64_t)(blk - acc) * kChunk;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kBlock) sgd_multi_kernel(TensorList tl, int32_t* step,
-                                                           SgdHyper h) {
+                                                           SgdHyper h, const float* gcoef) {
+  if (gcoef != nullptr) h.gscale *= *gcoef;
   int t;
   int64_t start;
   locate_chunk(tl.numel, tl.n, blockIdx.x, t, start);
@@ -171,7 +164,8 @@ __global__ void __launch_bounds__(kBlock) sgd_multi_kernel(TensorList tl, int32_
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) adam_multi_kernel(TensorList tl, const int32_t* step,
-                                                            AdamHyper h) {
+                                                            AdamHyper h, const float* gcoef) {
+  if (gcoef != nullptr) h.gscale *= *gcoef;
   int t;
   int64_t start;
   locate_chunk(tl.numel, tl.n, blockIdx.x, t, start);
@@ -231,57 +225,53 @@ inline int grid_for(int64_t n, int per_thread = 4) {
   if (g > 2048) g = 2048;  // 256 CUs x 8 blocks, grid-stride the rest
   return (int)g;
 }
-template <typename L>
-int chunk_blocks(const L& l) {
-  int b = 0;
-  for (int i = 0; i < l.n; ++i) b += (int)((l.numel[i] + kChunk - 1) / kChunk);
-  return b;
-}
 
 }  // namespace
 
 hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
                     float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s) {
+                    float grad_scale, hipStream_t s, const float* gcoef) {
   if (n <= 0) return hipSuccess;
   SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
-  hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, p, g, mom, step, n, h);
+  hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, p, g, mom, step, n, h,
+                     gcoef);
   if (step) hipLaunchKernelGGL(sgd_step_inc, dim3(1), dim3(1), 0, s, step);
   return hipGetLastError();
 }
 
 hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
                      float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s) {
+                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef) {
   if (n <= 0) return hipSuccess;
   AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
-  hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, p, g, m, v, step, n, h);
+  hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, p, g, m, v, step, n, h,
+                     gcoef);
   return hipGetLastError();
 }
 
 hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
                      float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s) {
+                     hipStream_t s, const float* gcoef) {
   const int nb = chunk_blocks(tl);
   if (nb == 0) return hipSuccess;
   SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
   if (dtype == kF32)
-    hipLaunchKernelGGL(sgd_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h);
+    hipLaunchKernelGGL(sgd_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
   else
-    hipLaunchKernelGGL(sgd_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h);
+    hipLaunchKernelGGL(sgd_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
   return hipGetLastError();
 }
 
 hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s) {
+                      hipStream_t s, const float* gcoef) {
   const int nb = chunk_blocks(tl);
   if (nb == 0) return hipSuccess;
   AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
   if (dtype == kF32)
-    hipLaunchKernelGGL(adam_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h);
+    hipLaunchKernelGGL(adam_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
   else
-    hipLaunchKernelGGL(adam_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h);
+    hipLaunchKernelGGL(adam_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
   return hipGetLastError();
 }
 

@@ -14,7 +14,10 @@ names, per-parameter state keys ``momentum_buffer`` / ``exp_avg`` /
     device int32 counters, so ``step()`` is hipGraph-capturable (no host reads);
     one counter per cohort (:class:`_StepCounters`), so every parameter counts
     its own updates as in ``torch.optim`` and a group may mix dtypes;
-  * CPU parameters use eager ATen math (plumbing tests).
+  * CPU parameters use eager ATen math (plumbing tests);
+  * a gradient-clipping coefficient (:mod:`.clip`, fused mode) can be armed for the next
+    ``step()``: a device float per device that the kernels multiply into the gradient as
+    they load it, so the clipped gradients are never written.
 """
 from __future__ import annotations
 
@@ -89,7 +92,24 @@ class _StepCounters:
         return out
 
 
-class FusedSGD(Optimizer):
+class _GradCoef:
+    """Fused gradient clipping: :meth:`arm_grad_coef` hands the next ``step()`` one float32
+    tensor per device, the clip coefficient; that step multiplies every gradient by it where
+    ``maximize``'s sign is applied (``p.grad`` itself keeps the unclipped values) and disarms.
+    A ``step()`` that was not armed is unchanged."""
+
+    _grad_coef: dict | None = None
+
+    def arm_grad_coef(self, coefs: dict) -> None:
+        """``coefs``: {torch.device: 1-element float32 tensor on that device}."""
+        self._grad_coef = dict(coefs)
+
+    def _take_grad_coef(self) -> dict:
+        coefs, self._grad_coef = self._grad_coef, None
+        return coefs or {}
+
+
+class FusedSGD(_GradCoef, Optimizer):
     """``bf16_shadow=True``: every f32 GPU parameter also gets a bf16 copy of its
     updated value, written by the same update kernel (``p._ptdt_bf16``); under bf16
     autocast :func:`ops.conv.cast_weight` uses it instead of casting the weight in
@@ -141,20 +161,22 @@ class FusedSGD(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        coefs = self._take_grad_coef()
         for gi, group in enumerate(self.param_groups):
             lr, mu, damp, wd, nest = (group["lr"], group["momentum"], group["dampening"],
                                       group["weight_decay"], group["nesterov"])
             gscale = -1.0 if group["maximize"] else 1.0
             for (device, dtype), ps in _split_by_device(group["params"]).items():
+                gcoef = coefs.get(device)
                 if device.type != "cuda":
-                    self._cpu_step(ps, lr, mu, damp, wd, nest, gscale)
+                    self._cpu_step(ps, lr, mu, damp, wd, nest, gscale, gcoef)
                     continue
                 # before creating buffers: a parameter's "first step" is decided here
                 for step, cps in self._cohorts.cohorts(ps, self._started):
-                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale)
+                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef)
         return loss
 
-    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale):
+    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None):
         grads = [p.grad for p in ps]
         moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
         C = native()
@@ -167,16 +189,18 @@ class FusedSGD(Optimizer):
         if (dtype == torch.float32 and aligned and pflat is not None and gflat is not None
                 and (not moms or mflat is not None) and not shadows):
             # one launch for the whole cohort (also increments the device counter)
-            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale)
+            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale, gcoef)
         else:
-            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows)
+            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows, gcoef)
             step.add_(1)
         for p in ps if shadows else ():
             p._ptdt_bf16_version = p._version  # the shadow is current until p changes
 
-    def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale):
+    def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale, gcoef=None):
         for p in ps:
             d = p.grad * gscale
+            if gcoef is not None:
+                d = d * gcoef
             if wd != 0:
                 d = d.add(p, alpha=wd)
             if mu != 0:
@@ -190,7 +214,7 @@ class FusedSGD(Optimizer):
             p.add_(d, alpha=-lr)
 
 
-class FusedAdam(Optimizer):
+class FusedAdam(_GradCoef, Optimizer):
     """Adam / AdamW (``decoupled_weight_decay=True``) with fp32 state."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -223,15 +247,17 @@ class FusedAdam(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        coefs = self._take_grad_coef()
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             gscale = -1.0 if group["maximize"] else 1.0
             for (device, dtype), sub in _split_by_device(group["params"]).items():
+                gcoef = coefs.get(device)
                 for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
                     step.add_(1)
                     ms, vs = self._state_lists(ps)
                     if device.type != "cuda":
-                        self._cpu_step(ps, ms, vs, step, group, gscale)
+                        self._cpu_step(ps, ms, vs, step, group, gscale, gcoef)
                         continue
                     C = native()
                     grads = [p.grad for p in ps]
@@ -241,10 +267,10 @@ class FusedAdam(Optimizer):
                     aligned = same_layout(pdata, grads) and same_layout(pdata, ms) and same_layout(pdata, vs)
                     if dtype == torch.float32 and aligned and None not in (pflat, gflat, mflat, vflat):
                         C.adam_flat_(pflat, gflat, mflat, vflat, step, group["lr"], b1, b2, group["eps"],
-                                     group["weight_decay"], group["decoupled_weight_decay"], gscale)
+                                     group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef)
                     else:
                         C.adam_multi_(pdata, grads, ms, vs, step, group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], group["decoupled_weight_decay"], gscale)
+                                      group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef)
         return loss
 
     def state_dict(self):
@@ -282,7 +308,7 @@ class FusedAdam(Optimizer):
                             v.copy_(loaded[p][1])
 
     @staticmethod
-    def _cpu_step(ps, ms, vs, step, group, gscale):
+    def _cpu_step(ps, ms, vs, step, group, gscale, gcoef=None):
         t = float(step.item())
         b1, b2 = group["betas"]
         lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
@@ -290,6 +316,8 @@ class FusedAdam(Optimizer):
         bc2s = (1 - b2 ** t) ** 0.5
         for p, m, v in zip(ps, ms, vs):
             g = p.grad.float() * gscale
+            if gcoef is not None:
+                g = g * gcoef
             if group["decoupled_weight_decay"]:
                 p.mul_(1 - lr * wd)
             elif wd != 0:

@@ -30,7 +30,8 @@ Engines (same observable result, different execution):
 Extras: rank-0 snapshots every ``save_every`` epochs with resume
 (``snapshot_path``; every engine saves its optimizer state in torch.optim.SGD
 layout, so snapshots interchange between engines), fault injection hooks,
-JSONL metrics.
+JSONL metrics. ``max_grad_norm=X`` clips the gradient norm between backward and
+step (ops/clip.py; autograd engine only, which ``engine="auto"`` then selects).
 """
 from __future__ import annotations
 
@@ -42,8 +43,10 @@ import torch.nn as nn
 
 from .._ext import native
 from ..data.loader import DeviceDataLoader
+from ..ops.clip import GradClipper
 from ..ops.fused_step import FusedMLPStep, _linears
 from ..ops.loss import cross_entropy
+from ..ops.optim import FusedAdam, FusedSGD
 from ..parallel import comm as comm_mod
 from ..parallel import env
 from ..parallel.ddp import DistributedDataParallel, _flatten_broadcast
@@ -86,7 +89,8 @@ class Trainer:
     def __init__(self, model: nn.Module, train_dataloader, optimizer: torch.optim.Optimizer, gpu_id: int | None = None,
                  *, loss_fn=None, engine: str = "auto", graph: bool = True, comm=None,
                  snapshot_path: str | None = None, save_every: int = 0, metrics_path: str | None = None,
-                 log=print, ddp_kwargs: dict | None = None, verbose: bool = True):
+                 log=print, ddp_kwargs: dict | None = None, verbose: bool = True,
+                 max_grad_norm: float | None = None):
         self.gpu_id = env.local_rank() if gpu_id is None else gpu_id
         self.device = torch.device("cuda", self.gpu_id) if torch.cuda.is_available() else torch.device("cpu")
         self.rank = env.rank()
@@ -96,6 +100,8 @@ class Trainer:
         self.loss_fn = loss_fn or cross_entropy
         self.log = log if verbose else (lambda *a, **k: None)
         self.graph = graph
+        self.max_grad_norm = max_grad_norm
+        self._clipper = None
         self.snapshot_path = snapshot_path
         self.save_every = save_every
         self.epochs_run = 0
@@ -153,6 +159,11 @@ class Trainer:
         return True
 
     def _select_engine(self, engine: str, model) -> str:
+        if self.max_grad_norm is not None:  # the fused / persistent engines have no clipping
+            if engine in ("fused", "persistent"):
+                raise ValueError(f"{engine} engine does not clip gradients: max_grad_norm needs engine='autograd'")
+            if engine == "auto":
+                return "autograd"
         if engine == "auto":
             return "persistent" if self._fusable(model) else "autograd"
         if engine in ("fused", "persistent") and not self._fusable(model):
@@ -174,8 +185,18 @@ class Trainer:
         with trace("bwd"):
             loss.backward()
         with trace("opt"):
+            if self.max_grad_norm is not None:
+                self._clip()
             self.optimizer.step()
         return loss
+
+    def _clip(self):
+        """Clip between backward() and step(): fused into the update for FusedSGD / FusedAdam (p.grad
+        stays unclipped), in place for any other optimizer."""
+        if self._clipper is None:
+            fused = self.optimizer if isinstance(self.optimizer, (FusedSGD, FusedAdam)) else None
+            self._clipper = GradClipper(list(self.model.parameters()), self.max_grad_norm, optimizer=fused)
+        return self._clipper()
 
     def _first_batch_size(self) -> int:
         dl = self.train_dataloader
