@@ -17,6 +17,7 @@
 #include "comm/xgmi_comm.h"
 #include "kernels/chunks.h"
 #include "kernels/kernels.h"
+#include "kernels/wave_loop_schedule.h"
 #include "reducer/reducer.h"
 
 namespace py = pybind11;
@@ -1841,6 +1842,26 @@ PYBIND11_MODULE(_C, m) {
         py::arg("has_bias") = true, py::arg("momentum") = 0.0, py::arg("weight_decay") = 0.0,
         py::arg("stamps") = false);
   m.def("fused_mlp_lds_bytes", [](int B, int Din, int H, int Dout) { return fused_mlp_lds_bytes(B, Din, H, Dout); });
+  // The lean wave loop's control (wave_loop_schedule.h) for a launch of n steps from (e0, j0) over epochs
+  // of S batches of B entries: (read offsets, barrier-in-front flags, loss ring slots, barriers taken,
+  // list stride). The kernel runs the same functions.
+  m.def(
+      "wave_loop_schedule",
+      [](int S, int B, int e0, int j0, int n, int depth) {
+        TORCH_CHECK(S > 0 && B > 0 && j0 >= 0 && j0 < S && n >= 0 && depth > 0, "wave_loop_schedule: bad arguments");
+        const int estride = wave_list_stride(S * B, B), ring = 2 * S + depth;
+        std::vector<int> ofs(n + depth + 2), slots(n + 1);
+        std::vector<unsigned char> bar(ofs.size());
+        int barriers = 0;
+        const int nr = wave_loop_enumerate(S, B, estride, e0, j0, n, depth, ring, ofs.data(), bar.data(), (int)ofs.size(),
+                                           slots.data(), (int)slots.size(), &barriers);
+        TORCH_CHECK(nr >= 0, "wave_loop_schedule: more reads or steps than a launch of n steps has");
+        ofs.resize(nr);
+        slots.resize(n);
+        std::vector<int> flags(bar.begin(), bar.begin() + nr);
+        return py::make_tuple(ofs, flags, slots, barriers, estride);
+      },
+      py::arg("S"), py::arg("B"), py::arg("e0"), py::arg("j0"), py::arg("n"), py::arg("depth") = kWavePrefetch);
   // gcoef (optional, last): a device float multiplied into the gradient scale, the clip coefficient
   m.def("sgd_flat_", &sgd_flat_, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("step"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "sampler.h"
+#include "wave_loop_schedule.h"
 
 namespace ptdt {
 namespace lw {
@@ -1067,6 +1068,20 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
 // on, every batch full with B == 16 R rows, no stamps -- so the code a plan never runs is not in the
 // object (one step loop instead of five). Barriers, LDS layout, list handling, prefetch depth and
 // every floating-point operation and its order are the generic kernel's: the results are its bits.
+//
+// The lean step loop issues the step's math and little else. Its control is wave_loop_schedule.h
+// (host-checked against the generic read_index rule): a launch runs whole kNB-step groups in one
+// unrolled body, then the n % kNB last steps without gathers.
+//   unchecked group : all its reads inside the current epoch list, all its slots inside the loss ring:
+//                     no wrap, barrier or ring test; the list entries (lp, lp_y) and the ring slot (rp)
+//                     are running per-lane addresses; one wait per batch, where the step first
+//                     touches it;
+//   checked group   : the same body under a uniform flag: every step is followed by a checked read
+//                     (list switch, epoch barrier, address reset) and a checked ring slot;
+//   loss share      : stored raw; reduce_losses in the helper waves applies the owner mask and the
+//                     1/rows scale per share, in the trainer's order, before its fixed-order sum;
+//   barriers        : T epoch barriers + the final one whatever the loop did (topped up after the loop).
+// The generic variant keeps the per-step loop below unchanged: it is the bitwise oracle.
 template <int R, int KP, int DOUT, int LOSS, bool AR, int VAR = kWaveGeneric>
 __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a, PersistArgs pa) {
   static_assert(R == 1 || R == 2 || R == 4, "rows per lane: 1, 2 or 4");
@@ -1099,6 +1114,13 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   } else {
     asm volatile("" ::"s"(tl_p), "s"(Din), "s"(ns_arg), "s"(has_start), "s"(start_e), "s"(start_j), "s"(has_bias_arg),
                  "s"(ldx_arg), "s"(cursor_p), "s"(P_arg), "s"(X_arg));
+    // has_start, start_e, start_j arrive as one 16-byte load whose fourth dword (the padding in front
+    // of pa.tl) is dead. The register allocator handed that register to another load of this batch,
+    // which then had to wait for the first: two kernel-argument round trips at entry (+0.2 us of
+    // prologue in the timeline). Keeping the dword alive up to here keeps the batch one round trip.
+    static_assert(offsetof(PersistArgs, tl) == offsetof(PersistArgs, start_j) + 8, "padding dword after start_j");
+    const int pad_arg = (&pa.start_j)[1];
+    asm volatile("" ::"s"(pad_arg), "s"(start_j), "s"(ldx_arg), "s"(has_bias_arg));
     if constexpr (VAR == kWaveLeanMom) asm volatile("" ::"s"(mom_arg), "s"(momentum_arg));
   }
   const int n = pa.n_steps, n_rows_arg = pa.N, loss_ring_arg = pa.loss_ring, nesterov = a.nesterov,
@@ -1229,13 +1251,42 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       const int grp = ht >> 4, sub = ht & 15, ngrp = hn >> 4;
       for (int64_t P = lo + grp; P < hi; P += ngrp) {
         const float* sh = lring + ((int)(P - pos0) % ring) * 64;
-        const float4 v = *reinterpret_cast<const float4*>(sh + 4 * sub);
+        float4 v = *reinterpret_cast<const float4*>(sh + 4 * sub);
+        if constexpr (LEAN && LOSS != kLossCEIndex) {
+          // the lean trainer stores each lane's loss unmasked and unscaled: the owner select (a batch
+          // row counted once; a non-owner's NaN becomes 0) and the 1/rows scale are applied here, per
+          // share and in the trainer's order, so the values added are the generic kernel's bits.
+          // Shares 4 sub .. 4 sub + 3 are lanes of DPP row sub / 4.
+          const int sq = sub >> 2;
+          const bool own = SCATTER ? (R == 4 || sq < 2) : sq == 0;
+          v.x = (own ? v.x : 0.f) * inv_full;
+          v.y = (own ? v.y : 0.f) * inv_full;
+          v.z = (own ? v.z : 0.f) * inv_full;
+          v.w = (own ? v.w : 0.f) * inv_full;
+        }
         const float acc = group_sum<16>((v.x + v.y) + (v.z + v.w));
         if (sub == 0) pa.losses[P - pos0] = acc;
       }
       lo = hi > lo ? hi : lo;
     };
     if (ht == 0 && pa.idx == nullptr) list_cache_publish(lc, e0);  // every thread's entries written (barrier)
+    if constexpr (LEAN) {
+      // The barriers, list builds and reductions of the generic form below, with one copy each of the
+      // list builder and of reduce_losses (the instruction cache is cold at every launch). Round 0
+      // builds epoch e0 + 1 in front of barrier 1; round i = 1 .. T follows epoch barrier i; round
+      // T + 1 follows the trainer's final barrier (T >= 0: a launch has n >= 1 steps, the host
+      // returns early for n_steps <= 0, so that barrier is always taken, as the trainer takes it).
+      for (int i = 0; i <= T + 1; ++i) {
+        if (i > 0) __syncthreads();
+        if (i > 0 && i <= T && ht == 0 && pa.idx == nullptr) list_cache_publish(lc, e0 + i);  // built before barrier i
+        if (i < T)
+          rank_epoch_indices_or(given_list(pa, e0 + i + 1), list(e0 + i + 1), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples,
+                                pa.seed, e0 + i + 1, pa.shuffle, ht, hn, lc);
+        // at barrier i the trainer has trained every position before (e0 + i) * S - kNB
+        if (i > 0) reduce_losses(i <= T ? min((int64_t)(e0 + i) * S - kNB, pos0 + n) : pos0 + n);
+      }
+      return;
+    }
     if (T > 0)  // epoch e0+1, needed at the trainer's first barrier
       rank_epoch_indices_or(given_list(pa, e0 + 1), list(e0 + 1), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples, pa.seed, e0 + 1,
                             pa.shuffle, ht, hn, lc);
@@ -1302,6 +1353,34 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   auto fetch = [&](Batch<R, KP, DOUT, RY>& f) {
     load_batch(f, sel_next, sel_y_next, nb_next);
     read_index();
+  };
+  // Lean variants: the loop control is wave_loop_schedule.h's (kNB-step groups, unchecked while they
+  // stay inside one epoch list and the loss ring, checked otherwise). The list entries and the loss
+  // ring slot are running per-lane addresses; a checked read / slot resets them at a wrap.
+  WaveLoopSchedule sch;
+  const int* lp = elist;     // this lane's entries of the next read (rows rho * 16 + i)
+  const int* lp_y = elist;   // its own loss row's entry (SCATTER)
+  float* rp = lring + lane;  // this lane's share in the next step's ring slot
+  if constexpr (LEAN) {
+    sch.init(S, B, estride, e0, j0, n, kNB, ring);
+    nb_next = B;
+  }
+  auto read_run = [&]() {
+#pragma unroll
+    for (int rho = 0; rho < R; ++rho) sel_next[rho] = lp[rho * 16];
+    if constexpr (SCATTER) sel_y_next = lp_y[0];
+    lp += B;
+    lp_y += B;
+  };
+  auto read_checked = [&]() {
+    bool bar, switched;
+    const int o = sch.next(&bar, &switched);
+    if (bar) __syncthreads();  // new epoch: its list is ready, the old one free
+    if (switched) {
+      lp = elist + o + i;
+      lp_y = lp + rho_own * 16;
+    }
+    read_run();
   };
 
   Ticks tk;
@@ -1384,6 +1463,23 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     constexpr bool MOM = SGD == kSgdMom;
     constexpr bool RING = decltype(ring_tag)::value;
     const int nb = f.nb;
+    if constexpr (LEAN) {
+      // The batch was requested kNB steps ago: one wait for all of it here. Every loaded register
+      // passes through an empty asm, so the compiler places its wait for the batch's last load in
+      // front of the first one and none later (it had one in front of each load's first use).
+#pragma unroll
+      for (int ry = RY - 1; ry >= 0; --ry) {
+        if constexpr (LOSS == kLossCEIndex) asm volatile("" : "+v"(f.yi[ry]));
+#pragma unroll
+        for (int c = DOUT - 1; c >= 0; --c)
+          if constexpr (LOSS != kLossCEIndex) asm volatile("" : "+v"(f.y[ry][c]));
+      }
+#pragma unroll
+      for (int rho = R - 1; rho >= 0; --rho) {
+#pragma unroll
+        for (int k = KP - 1; k >= 0; --k) asm volatile("" : "+v"(f.x[rho][k]));
+      }
+    }
     // ---- forward: partial logits of this feature group
     float zp[R][DOUT];
 #pragma unroll
@@ -1394,6 +1490,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     tk.tick(1);
     // ---- logits -> loss -> dL/dz (g[rho][c] in every lane)
     float g[R][DOUT], lsum, csum;
+    float lraw;  // lsum before the owner select (lean: the helper waves apply it)
     if constexpr (SCATTER) {
       float z;
       if constexpr (R == 2) {
@@ -1407,6 +1504,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       row_loss(&z, f.y[0], f.yi[0], LEAN || rho_own * 16 + i < nb, &gz, l, cnt);
       // each batch row counted once: R == 2 has every row in two DPP rows
       const bool owner = R == 4 || q < 2;
+      lraw = l;
       lsum = owner ? l : 0.f;
       csum = owner ? cnt : 0.f;
       if constexpr (LOSS != kLossCEIndex) gz *= f.cg;  // 1/B once
@@ -1436,6 +1534,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         lsum += l;
         csum += cnt;
       }
+      lraw = lsum;
       if (q != 0) {  // the 4 DPP rows computed the same rows: count them once
         lsum = 0.f;
         csum = 0.f;
@@ -1558,7 +1657,11 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       Gbk[c] = gb[c];
     }
     // ---- loss report
-    if constexpr (RING) {  // this lane's share; the helper waves add the 64 shares
+    if constexpr (LEAN) {  // running slot address; mask and scale left to the helper waves (reduce_losses)
+      if constexpr (LOSS == kLossCEIndex) *rp = !(csum > 0.f) ? NAN : lsum * inv_denom;
+      else *rp = lraw;
+      rp += 64;
+    } else if constexpr (RING) {  // this lane's share; the helper waves add the 64 shares
       const float share = (LOSS == kLossCEIndex && !(csum > 0.f)) ? NAN : lsum * inv_denom;
       lring[rslot * 64 + lane] = share;
       rslot = rslot + 1 == ring ? 0 : rslot + 1;
@@ -1571,9 +1674,20 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   };
 
   tk.start();
-  read_index();
+  if constexpr (LEAN) {
+    lp = elist + sch.first() + i;  // j0 < S: the first read needs no check
+    lp_y = lp + rho_own * 16;
+    read_run();
 #pragma unroll
-  for (int u = 0; u < kNB; ++u) fetch(buf[u]);
+    for (int u = 0; u < kNB; ++u) {
+      load_batch(buf[u], sel_next, sel_y_next, B);
+      read_checked();
+    }
+  } else {
+    read_index();
+#pragma unroll
+    for (int u = 0; u < kNB; ++u) fetch(buf[u]);
+  }
   tk.tick(0);
   int done = 0;
   const int nfull = n - n % kNB;
@@ -1598,13 +1712,48 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // one loop instantiation per (SGD kind, loss ring): no per-step branch on either. Plain SGD (the
   // reference's SGD(lr)) has its own loop with the ring only; without the ring it takes the
   // weight-decay loop (same values: d = g + 0 * w).
+  // lean: one unrolled group body (three register buffers in turn). Unchecked, a step is followed by
+  // a read at the running address; checked (a uniform per-group flag), by a checked read and ring slot.
+  // The n % kNB steps after the last group gather nothing.
+  auto run_lean = [&](auto sgd_tag) {
+    if (failed) return;
+    done = wave_loop_run(
+        sch, n,
+        [&](WaveLoopSchedule& c, bool checked) {
+#pragma unroll
+          for (int u = 0; u < kNB; ++u) {
+            train(buf[u], 0, sgd_tag, std::true_type{});
+            load_batch(buf[u], sel_next, sel_y_next, B);
+            if (__builtin_expect(checked, 0)) {  // laid out behind the loop: the unchecked path falls through
+              read_checked();
+              if (c.slot_done()) rp = lring + lane;
+            } else {
+              read_run();
+            }
+          }
+          if (!checked) c.advance();
+          return !failed;
+        },
+        [&](WaveLoopSchedule& c, int left) {
+          int k = 0;
+#pragma unroll
+          for (int u = 0; u < kNB - 1; ++u) {
+            if (u < left && !failed) {
+              train(buf[u], 0, sgd_tag, std::true_type{});
+              if (c.slot_done()) rp = lring + lane;
+              ++k;
+            }
+          }
+          return k;
+        });
+  };
   using Plain = std::integral_constant<int, kSgdPlain>;
   using NoMom = std::integral_constant<int, kSgdNoMom>;
   using Mom = std::integral_constant<int, kSgdMom>;
   if constexpr (VAR == kWaveLeanPlain) {  // the plan's loop is the only one in a lean kernel
-    run(Plain{}, std::true_type{});
+    run_lean(Plain{});
   } else if constexpr (VAR == kWaveLeanMom) {
-    run(Mom{}, std::true_type{});
+    run_lean(Mom{});
   } else if (use_mom) {
     if (ring) run(Mom{}, std::true_type{});
     else run(Mom{}, std::false_type{});
@@ -1654,6 +1803,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
     }
   }
+  if constexpr (LEAN) barriers = sch.barriers;
   while (barriers < T) {
     __syncthreads();
     ++barriers;
