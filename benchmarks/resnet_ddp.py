@@ -68,6 +68,12 @@ def main(argv=None):
                     help="clip the gradient 2-norm to this value between backward and step: ops.clip.GradClipper "
                          "fused into FusedSGD (native; captured with the step) or torch.nn.utils.clip_grad_norm_ "
                          "(--impl torch). Default: off")
+    ap.add_argument("--lr_schedule", default="none", choices=["none", "warmup_cosine", "warmup_step"],
+                    help="learning-rate schedule stepped after every optimizer step: linear warm-up 0.1 -> 1 over "
+                         "--lr_warmup_steps, then cosine to 0 over the rest of the run, or x0.1 every third of it. "
+                         "ops.lr_scheduler (native; the rate lives on the device and the schedule is captured with "
+                         "the step) or torch.optim.lr_scheduler (--impl torch). Default: none")
+    ap.add_argument("--lr_warmup_steps", type=int, default=5, help="warm-up length of --lr_schedule")
     a = ap.parse_args(argv)
     torch.backends.cudnn.benchmark = not a.no_cudnn_benchmark and not a.deterministic
     torch.backends.cudnn.deterministic = a.deterministic
@@ -109,6 +115,19 @@ def main(argv=None):
         from pytorch_distributed_training_tutorials_amd.ops.clip import GradClipper
 
         clipper = GradClipper(list(model.parameters()), a.clip_grad_norm, optimizer=opt)  # created once
+    sched = None
+    if a.lr_schedule != "none":  # created once, before any capture: its device buffers are static
+        if a.impl == "native":
+            from pytorch_distributed_training_tutorials_amd.ops import lr_scheduler as S
+        else:
+            from torch.optim import lr_scheduler as S
+        # the steps the run executes are only known at its end: the schedule spans a nominal
+        # --steps + --warmup after its warm-up (cosine is periodic and step decay goes on past it)
+        span = max(3, a.steps + a.warmup)
+        after = (S.CosineAnnealingLR(opt, T_max=span) if a.lr_schedule == "warmup_cosine"
+                 else S.StepLR(opt, step_size=max(1, span // 3), gamma=0.1))
+        sched = S.SequentialLR(opt, [S.LinearLR(opt, start_factor=0.1, end_factor=1.0, total_iters=a.lr_warmup_steps),
+                                     after], [a.lr_warmup_steps])
     x = torch.empty(a.batch_size, 3, a.image, a.image, device=dev)
     native().philox_(x, 1234 + rank, 0, 1)
     if not a.no_channels_last:
@@ -144,6 +163,8 @@ def main(argv=None):
         elif a.clip_grad_norm is not None:
             grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), a.clip_grad_norm, foreach=True)
         opt.step()
+        if sched is not None:
+            sched.step()  # native: one single-wave launch, no host read -- part of the captured step
         if a.loss_curve and not torch.cuda.is_current_stream_capturing():
             curve.append(loss.detach().clone())
         return loss
@@ -247,6 +268,9 @@ def main(argv=None):
             **({"clip_grad_norm": a.clip_grad_norm,
                 "grad_norm": float(clipper.norm if clipper is not None else grad_norm)}
                if a.clip_grad_norm is not None else {}),
+            **({"lr_schedule": a.lr_schedule, "lr_warmup_steps": a.lr_warmup_steps,
+                "lr_schedule_steps": int(sched.last_epoch), "last_lr": [float(v) for v in sched.get_last_lr()]}
+               if sched is not None else {}),
             "final_loss": final, "finite": True, "kernel_choices": _choices(), "steps_total": executed + a.steps, **({"tag": a.tag} if a.tag else {}),
         }), flush=True)
     env.destroy_process_group()

@@ -493,28 +493,40 @@ const float* gcoef_ptr(const c10::optional<Tensor>& gcoef, const Tensor& p) {
   return gcoef->data_ptr<float>();
 }
 
+// the optional device learning rate of the optimizer steps: the group's slot of a schedule's lr buffer
+const float* lr_dev_ptr(const c10::optional<Tensor>& lr_dev, const Tensor& p) {
+  if (!lr_dev.has_value() || !lr_dev->defined()) return nullptr;
+  TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == p.device() && lr_dev->scalar_type() == at::kFloat &&
+                  lr_dev->numel() == 1 && lr_dev->is_contiguous(),
+              "lr_dev must be one contiguous float32 value on the parameters' device");
+  return lr_dev->data_ptr<float>();
+}
+
 void sgd_flat_(Tensor p, Tensor g, c10::optional<Tensor> mom, c10::optional<Tensor> step, double lr,
                double momentum, double dampening, double wd, bool nesterov, double grad_scale,
-               c10::optional<Tensor> gcoef) {
+               c10::optional<Tensor> gcoef, c10::optional<Tensor> lr_dev) {
   check_gpu(p, "param");
   check_gpu(g, "grad");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && p.numel() == g.numel());
   c10::hip::HIPGuard guard(p.device().index());
   hip_check(sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), ptr_or_null<float>(mom),
                      ptr_or_null<int32_t>(step), p.numel(), (float)lr, (float)momentum, (float)dampening,
-                     (float)wd, nesterov, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p)),
+                     (float)wd, nesterov, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p),
+                     lr_dev_ptr(lr_dev, p)),
             "sgd_flat");
 }
 
 void adam_flat_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, double lr, double b1, double b2,
-                double eps, double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef) {
+                double eps, double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef,
+                c10::optional<Tensor> lr_dev) {
   check_gpu(p, "param");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.numel() == p.numel() && m.numel() == p.numel() &&
               v.numel() == p.numel() && step.scalar_type() == at::kInt);
   c10::hip::HIPGuard guard(p.device().index());
   hip_check(adam_flat(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                       step.data_ptr<int32_t>(), p.numel(), (float)lr, (float)b1, (float)b2, (float)eps,
-                      (float)wd, decoupled, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p)),
+                      (float)wd, decoupled, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p),
+                     lr_dev_ptr(lr_dev, p)),
             "adam_flat");
 }
 
@@ -525,7 +537,8 @@ void for_tensor_chunks(size_t n, F&& f) {
 
 void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> moms,
                 c10::optional<Tensor> step, double lr, double momentum, double dampening, double wd,
-                bool nesterov, double grad_scale, std::vector<Tensor> shadows, c10::optional<Tensor> gcoef) {
+                bool nesterov, double grad_scale, std::vector<Tensor> shadows, c10::optional<Tensor> gcoef,
+                c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
   TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
   TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat),
@@ -553,14 +566,16 @@ void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tens
       }
     }
     hip_check(sgd_multi(tl, dt, ptr_or_null<int32_t>(step), (float)lr, (float)momentum, (float)dampening,
-                        (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0])),
+                        (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
+                        lr_dev_ptr(lr_dev, ps[0])),
               "sgd_multi");
   });
 }
 
 void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> ms,
                  std::vector<Tensor> vs, Tensor step, double lr, double b1, double b2, double eps,
-                 double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef) {
+                 double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef,
+                c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
   TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
   const int dt = dt_of(ps[0]);
@@ -582,7 +597,8 @@ void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
       tl.s2[i - a] = vs[i].data_ptr<float>();
     }
     hip_check(adam_multi(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)b1, (float)b2, (float)eps,
-                         (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0])),
+                         (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
+                        lr_dev_ptr(lr_dev, ps[0])),
               "adam_multi");
   });
 }
@@ -645,6 +661,52 @@ void clip_clamp_(std::vector<Tensor> spans, double c) {
   const SpanList sl = span_list(spans, "clip_clamp_");
   c10::hip::HIPGuard guard(spans[0].device().index());
   hip_check(clip_clamp(sl, dt_of(spans[0]), (float)c, cur_stream(spans[0])), "clip_clamp");
+}
+
+// ------------------------------------------------------------- learning-rate schedules
+// One launch: t += increment, lr[g] = base_lrs[g] * f(t). The program arrives as parallel lists, one
+// entry per segment (ops/lr_scheduler.py builds and validates them; the caps are checked again here).
+void lr_schedule_step_(Tensor t, Tensor lr, std::vector<double> base_lrs, std::vector<int64_t> bounds,
+                       std::vector<int64_t> kinds, std::vector<int64_t> ns, std::vector<double> as,
+                       std::vector<double> bs, std::vector<std::vector<int64_t>> milestones, bool increment) {
+  const size_t S = kinds.size();
+  TORCH_CHECK(S >= 1 && S <= (size_t)kLrMaxSegments, "lr_schedule_step_: 1..", kLrMaxSegments, " segments, got ", S);
+  TORCH_CHECK(ns.size() == S && as.size() == S && bs.size() == S && milestones.size() == S && bounds.size() == S - 1,
+              "lr_schedule_step_: one n, a, b and milestone list per segment, segments - 1 bounds");
+  TORCH_CHECK(!base_lrs.empty() && base_lrs.size() <= (size_t)kLrMaxGroups, "lr_schedule_step_: 1..", kLrMaxGroups,
+              " parameter groups per launch, got ", base_lrs.size());
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.numel() == 1, "lr_schedule_step_: t must be int32[1]");
+  TORCH_CHECK(lr.is_cuda() && lr.device() == t.device() && lr.scalar_type() == at::kFloat && lr.is_contiguous() &&
+                  lr.numel() == (int64_t)base_lrs.size(),
+              "lr_schedule_step_: lr must be float32[groups] on t's device");
+  constexpr int64_t kMaxT = std::numeric_limits<int32_t>::max();
+  LrProgram prog{};
+  prog.groups = (int)base_lrs.size();
+  prog.segments = (int)S;
+  for (size_t g = 0; g < base_lrs.size(); ++g) prog.base[g] = base_lrs[g];
+  for (size_t k = 0; k + 1 < S; ++k) {
+    TORCH_CHECK(bounds[k] > (k ? bounds[k - 1] : 0) && bounds[k] <= kMaxT,
+                "lr_schedule_step_: bounds must be ascending positive int32 values");
+    prog.bound[k] = (int32_t)bounds[k];
+  }
+  for (size_t k = 0; k < S; ++k) {
+    LrSegment& sg = prog.seg[k];
+    TORCH_CHECK(kinds[k] >= 0 && kinds[k] < kLrKinds, "lr_schedule_step_: unknown segment kind ", kinds[k]);
+    TORCH_CHECK(ns[k] >= 0 && ns[k] <= kMaxT, "lr_schedule_step_: segment n out of range");
+    TORCH_CHECK(milestones[k].size() <= (size_t)kLrMaxMilestones, "lr_schedule_step_: at most ", kLrMaxMilestones,
+                " milestones per segment, got ", milestones[k].size());
+    sg.kind = (int)kinds[k];
+    sg.n = sg.kind == kLrMultiStep ? (int)milestones[k].size() : (int)ns[k];
+    sg.a = as[k];
+    sg.b = bs[k];
+    for (size_t i = 0; i < milestones[k].size(); ++i) {
+      TORCH_CHECK(milestones[k][i] >= 0 && milestones[k][i] <= kMaxT, "lr_schedule_step_: milestone out of range");
+      sg.ms[i] = (int32_t)milestones[k][i];
+    }
+  }
+  c10::hip::HIPGuard guard(t.device().index());
+  hip_check(lr_schedule_step(t.data_ptr<int32_t>(), lr.data_ptr<float>(), prog, increment ? 1 : 0, cur_stream(t)),
+            "lr_schedule_step");
 }
 
 void bucket_copy(std::vector<Tensor> ts, Tensor flat, double scale, bool unpack) {
@@ -1865,22 +1927,28 @@ PYBIND11_MODULE(_C, m) {
   // gcoef (optional, last): a device float multiplied into the gradient scale, the clip coefficient
   m.def("sgd_flat_", &sgd_flat_, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("step"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),
-        py::arg("gcoef") = py::none());
+        py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none());
   m.def("adam_flat_", &adam_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("decoupled"),
-        py::arg("grad_scale"), py::arg("gcoef") = py::none());
+        py::arg("grad_scale"), py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none());
   m.def("sgd_multi_", &sgd_multi_, py::arg("ps"), py::arg("gs"), py::arg("moms"), py::arg("step"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),
-        py::arg("shadows") = std::vector<Tensor>{}, py::arg("gcoef") = py::none());
+        py::arg("shadows") = std::vector<Tensor>{}, py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none());
   m.def("adam_multi_", &adam_multi_, py::arg("ps"), py::arg("gs"), py::arg("ms"), py::arg("vs"), py::arg("step"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("decoupled"),
-        py::arg("grad_scale"), py::arg("gcoef") = py::none());
+        py::arg("grad_scale"), py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none());
   m.def("clip_norm_partials_", &clip_norm_partials_, py::arg("spans"), py::arg("ws"), py::arg("first_slot"),
         py::arg("norm"), "per-chunk norm partials (norm 0: sum of squares, 1: max |g|); returns the slot count");
   m.def("clip_norm_finalize_", &clip_norm_finalize_, py::arg("ws"), py::arg("n"), py::arg("norm"), py::arg("max_norm"),
         py::arg("partial"), py::arg("rec"), "rec = {total_norm, clip_coef} from n partial slots");
   m.def("clip_scale_", &clip_scale_, py::arg("spans"), py::arg("rec"), "spans *= rec[1] (skipped when exactly 1)");
   m.def("clip_clamp_", &clip_clamp_, py::arg("spans"), py::arg("c"), "spans = clamp(spans, -c, c), NaN kept");
+  m.def("lr_schedule_step_", &lr_schedule_step_, py::arg("t"), py::arg("lr"), py::arg("base_lrs"), py::arg("bounds"),
+        py::arg("kinds"), py::arg("ns"), py::arg("as_"), py::arg("bs"), py::arg("milestones"), py::arg("increment"),
+        "t += increment; lr[g] = base_lrs[g] * schedule(t): one single-wave launch, capturable");
+  m.attr("LR_MAX_SEGMENTS") = kLrMaxSegments;
+  m.attr("LR_MAX_MILESTONES") = kLrMaxMilestones;
+  m.attr("LR_MAX_GROUPS") = kLrMaxGroups;
   m.def("bucket_copy", &bucket_copy);
   m.def("scale_", &scale_);
   m.def("cast_multi_", &cast_multi_, py::arg("dsts"), py::arg("srcs"));

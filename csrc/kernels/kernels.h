@@ -239,13 +239,17 @@ size_t torch_perm_lds_bytes(int n);
 // d = nesterov ? d + mu*buf : buf; p -= lr*d.
 // gcoef (all four): optional device float the kernel multiplies into grad_scale when it starts --
 // the gradient-clipping coefficient of gradclip.hip, applied without rewriting the gradients.
+// lr_dev (all four): optional device float that replaces lr when the kernel starts -- the group's
+// slot of a schedule's lr[G] buffer (lr_schedule.hip); AdamW's decoupled decay follows it too.
 hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
                     float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s, const float* gcoef = nullptr);
+                    float grad_scale, hipStream_t s, const float* gcoef = nullptr,
+                    const float* lr_dev = nullptr);
 // Adam/AdamW; step is a device counter already incremented for this step.
 hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
                      float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef = nullptr);
+                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef = nullptr,
+                     const float* lr_dev = nullptr);
 
 constexpr int kMaxTensorsPerLaunch = 32;
 struct TensorList {
@@ -259,10 +263,10 @@ struct TensorList {
 };
 hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
                      float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s, const float* gcoef = nullptr);
+                     hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
 hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s, const float* gcoef = nullptr);
+                      hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
 // dst[i] = src_i * scale over a list (bucket pack) or the reverse (unpack).
 struct CopyList {
   int n;
@@ -301,6 +305,40 @@ hipError_t clip_norm_finalize(const float* ws, int64_t n, int norm, float max_no
 hipError_t clip_scale(const SpanList& sl, int dtype, const float* rec, hipStream_t s);
 // g = min(max(g, -c), c), NaN kept (torch.clamp).
 hipError_t clip_clamp(const SpanList& sl, int dtype, float c, hipStream_t s);
+
+// --------------------------------------------------------------------------
+// Learning-rate schedules (csrc/kernels/lr_schedule.hip). A piecewise program: segment k is active
+// for bound[k-1] <= t < bound[k] (bound[-1] = 0, the last segment continues) and is evaluated at the
+// segment-local time t' = t - bound[k-1]; lr[g] = base[g] * f(t'), fp64 rounded once to float32.
+constexpr int kLrMaxSegments = 4;
+constexpr int kLrMaxMilestones = 16;  // of one multistep segment
+constexpr int kLrMaxGroups = 64;      // parameter groups per launch: one lane of the wave each
+enum LrKind : int {
+  kLrConstant = 0,     // a if t' < n else 1                                  (ConstantLR: factor, total_iters)
+  kLrLinear = 1,       // a + (b - a) * min(t', n) / n                        (LinearLR: start, end, total_iters)
+  kLrCosine = 2,       // r + (1 - r) * (1 + cos(pi t' / n)) / 2, r = a/base  (CosineAnnealingLR: eta_min, T_max)
+  kLrStep = 3,         // a ** (t' / n)                                       (StepLR: gamma, step_size)
+  kLrMultiStep = 4,    // a ** #{i < n: ms[i] <= t'}                          (MultiStepLR: gamma, milestones)
+  kLrExponential = 5,  // a ** t'                                             (ExponentialLR: gamma)
+  kLrPolynomial = 6,   // (1 - min(t', n) / n) ** b                           (PolynomialLR: total_iters, power)
+  kLrKinds = 7,
+};
+struct LrSegment {
+  int kind;
+  int n;
+  double a, b;
+  int32_t ms[kLrMaxMilestones];
+};
+struct LrProgram {
+  int groups, segments;
+  int32_t bound[kLrMaxSegments];  // segments - 1 ascending milestones
+  LrSegment seg[kLrMaxSegments];
+  double base[kLrMaxGroups];
+};
+// t (device int32) += increment ? 1 : 0, then lr[g] = schedule(t) for g < prog.groups. One wave,
+// capturable: reads no host memory, allocates nothing. hipErrorInvalidValue for a program outside
+// the caps above.
+hipError_t lr_schedule_step(int32_t* t, float* lr, const LrProgram& prog, int increment, hipStream_t s);
 
 // --------------------------------------------------------------------------
 // Losses (csrc/kernels/loss.hip). Row-wise log-softmax CE (soft or index

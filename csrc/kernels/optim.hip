@@ -63,8 +63,9 @@ __device__ __forceinline__ float adam_update(float p, float g, float* m, float* 
 __global__ void __launch_bounds__(kBlock) sgd_flat_kernel(float* __restrict__ p,
                                                           const float* __restrict__ g, float* mom,
                                                           int32_t* step, int64_t n, SgdHyper h,
-                                                          const float* gcoef) {
+                                                          const float* gcoef, const float* lr_dev) {
   if (gcoef != nullptr) h.gscale *= *gcoef;
+  if (lr_dev != nullptr) h.lr = *lr_dev;
   const bool first = step ? (*step == 0) : false;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t t0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -90,8 +91,10 @@ __global__ void sgd_step_inc(int32_t* step) { *step += 1; }
 __global__ void __launch_bounds__(kBlock) adam_flat_kernel(float* __restrict__ p,
                                                            const float* __restrict__ g, float* m,
                                                            float* v, const int32_t* step, int64_t n,
-                                                           AdamHyper h, const float* gcoef) {
+                                                           AdamHyper h, const float* gcoef,
+                                                           const float* lr_dev) {
   if (gcoef != nullptr) h.gscale *= *gcoef;
+  if (lr_dev != nullptr) h.lr = *lr_dev;
   const float t = (float)(*step);
   const float bc1 = 1.f - powf(h.b1, t);
   const float bc2s = sqrtf(1.f - powf(h.b2, t));
@@ -103,8 +106,10 @@ __global__ void __launch_bounds__(kBlock) adam_flat_kernel(float* __restrict__ p
 // ---------------------------------------------------------------- multi-tensor
 template <typename T>
 __global__ void __launch_bounds__(kBlock) sgd_multi_kernel(TensorList tl, int32_t* step,
-                                                           SgdHyper h, const float* gcoef) {
+                                                           SgdHyper h, const float* gcoef,
+                                                           const float* lr_dev) {
   if (gcoef != nullptr) h.gscale *= *gcoef;
+  if (lr_dev != nullptr) h.lr = *lr_dev;
   int t;
   int64_t start;
   locate_chunk(tl.numel, tl.n, blockIdx.x, t, start);
@@ -164,8 +169,10 @@ __global__ void __launch_bounds__(kBlock) sgd_multi_kernel(TensorList tl, int32_
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) adam_multi_kernel(TensorList tl, const int32_t* step,
-                                                            AdamHyper h, const float* gcoef) {
+                                                            AdamHyper h, const float* gcoef,
+                                                            const float* lr_dev) {
   if (gcoef != nullptr) h.gscale *= *gcoef;
+  if (lr_dev != nullptr) h.lr = *lr_dev;
   int t;
   int64_t start;
   locate_chunk(tl.numel, tl.n, blockIdx.x, t, start);
@@ -230,48 +237,52 @@ inline int grid_for(int64_t n, int per_thread = 4) {
 
 hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
                     float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s, const float* gcoef) {
+                    float grad_scale, hipStream_t s, const float* gcoef, const float* lr_dev) {
   if (n <= 0) return hipSuccess;
   SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
   hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, p, g, mom, step, n, h,
-                     gcoef);
+                     gcoef, lr_dev);
   if (step) hipLaunchKernelGGL(sgd_step_inc, dim3(1), dim3(1), 0, s, step);
   return hipGetLastError();
 }
 
 hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
                      float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef) {
+                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef, const float* lr_dev) {
   if (n <= 0) return hipSuccess;
   AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
   hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, p, g, m, v, step, n, h,
-                     gcoef);
+                     gcoef, lr_dev);
   return hipGetLastError();
 }
 
 hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
                      float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s, const float* gcoef) {
+                     hipStream_t s, const float* gcoef, const float* lr_dev) {
   const int nb = chunk_blocks(tl);
   if (nb == 0) return hipSuccess;
   SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
   if (dtype == kF32)
-    hipLaunchKernelGGL(sgd_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
+    hipLaunchKernelGGL(sgd_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
+                       lr_dev);
   else
-    hipLaunchKernelGGL(sgd_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
+    hipLaunchKernelGGL(sgd_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
+                       lr_dev);
   return hipGetLastError();
 }
 
 hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s, const float* gcoef) {
+                      hipStream_t s, const float* gcoef, const float* lr_dev) {
   const int nb = chunk_blocks(tl);
   if (nb == 0) return hipSuccess;
   AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
   if (dtype == kF32)
-    hipLaunchKernelGGL(adam_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
+    hipLaunchKernelGGL(adam_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
+                       lr_dev);
   else
-    hipLaunchKernelGGL(adam_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef);
+    hipLaunchKernelGGL(adam_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
+                       lr_dev);
   return hipGetLastError();
 }
 

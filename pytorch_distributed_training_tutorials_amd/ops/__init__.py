@@ -4,5 +4,7 @@ from .flat import FlatParameters, contiguous_span  # noqa: F401
 from .fused_step import FusedMLPStep  # noqa: F401
 from .linear import Linear, gemm, linear  # noqa: F401
 from .loss import CrossEntropyLoss, MSELoss, cross_entropy, mse_loss  # noqa: F401
+from .lr_scheduler import (ConstantLR, CosineAnnealingLR, ExponentialLR, LinearLR, MultiStepLR,  # noqa: F401
+                           PolynomialLR, SequentialLR, StepLR)
 from .norm import BatchNorm2d, SyncBatchNorm  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401

@@ -17,7 +17,10 @@ names, per-parameter state keys ``momentum_buffer`` / ``exp_avg`` /
   * CPU parameters use eager ATen math (plumbing tests);
   * a gradient-clipping coefficient (:mod:`.clip`, fused mode) can be armed for the next
     ``step()``: a device float per device that the kernels multiply into the gradient as
-    they load it, so the clipped gradients are never written.
+    they load it, so the clipped gradients are never written;
+  * a learning-rate schedule (:mod:`.lr_scheduler`) can be bound: a device float per
+    (group, device) that the kernels load in place of ``group["lr"]``, so the learning rate
+    moves inside a captured step.
 """
 from __future__ import annotations
 
@@ -109,7 +112,36 @@ class _GradCoef:
         return coefs or {}
 
 
-class FusedSGD(_GradCoef, Optimizer):
+class _DeviceLr:
+    """Device learning rates: while a scheduler of :mod:`.lr_scheduler` is bound, ``step()`` hands
+    the update kernels of each (group, device) that group's slot of the scheduler's ``lr`` buffer on
+    that device, and the kernels use it in place of ``group["lr"]`` (which stays a Python float; the
+    scheduler refreshes it at its host-read points). CPU parameters keep using ``group["lr"]``. An
+    optimizer with no scheduler bound is unchanged."""
+
+    _lr_scheduler = None
+    _lr_views: dict | None = None
+
+    def bind_lr_scheduler(self, scheduler, views: dict) -> None:
+        """``views``: {torch.device: [one 1-element float32 view per parameter group]}. A scheduler
+        bound earlier is released (its ``step()`` then raises)."""
+        old = self._lr_scheduler
+        if old is not None and old is not scheduler:
+            old._released()
+        self._lr_scheduler = scheduler
+        self._lr_views = dict(views)
+
+    def _lr_dev(self, gi: int, device):
+        if self._lr_views is None or device.type != "cuda":
+            return None
+        views = self._lr_views.get(device)
+        if views is None or gi >= len(views):
+            raise RuntimeError(f"the bound learning-rate scheduler has no buffer for group {gi} on {device}: "
+                               "parameters or groups were added after it was constructed")
+        return views[gi]
+
+
+class FusedSGD(_GradCoef, _DeviceLr, Optimizer):
     """``bf16_shadow=True``: every f32 GPU parameter also gets a bf16 copy of its
     updated value, written by the same update kernel (``p._ptdt_bf16``); under bf16
     autocast :func:`ops.conv.cast_weight` uses it instead of casting the weight in
@@ -171,12 +203,13 @@ class FusedSGD(_GradCoef, Optimizer):
                 if device.type != "cuda":
                     self._cpu_step(ps, lr, mu, damp, wd, nest, gscale, gcoef)
                     continue
+                lr_dev = self._lr_dev(gi, device)
                 # before creating buffers: a parameter's "first step" is decided here
                 for step, cps in self._cohorts.cohorts(ps, self._started):
-                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef)
+                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
         return loss
 
-    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None):
+    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None, lr_dev=None):
         grads = [p.grad for p in ps]
         moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
         C = native()
@@ -189,9 +222,9 @@ class FusedSGD(_GradCoef, Optimizer):
         if (dtype == torch.float32 and aligned and pflat is not None and gflat is not None
                 and (not moms or mflat is not None) and not shadows):
             # one launch for the whole cohort (also increments the device counter)
-            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale, gcoef)
+            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
         else:
-            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows, gcoef)
+            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows, gcoef, lr_dev)
             step.add_(1)
         for p in ps if shadows else ():
             p._ptdt_bf16_version = p._version  # the shadow is current until p changes
@@ -214,7 +247,7 @@ class FusedSGD(_GradCoef, Optimizer):
             p.add_(d, alpha=-lr)
 
 
-class FusedAdam(_GradCoef, Optimizer):
+class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
     """Adam / AdamW (``decoupled_weight_decay=True``) with fp32 state."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -253,6 +286,7 @@ class FusedAdam(_GradCoef, Optimizer):
             gscale = -1.0 if group["maximize"] else 1.0
             for (device, dtype), sub in _split_by_device(group["params"]).items():
                 gcoef = coefs.get(device)
+                lr_dev = self._lr_dev(gi, device)
                 for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
                     step.add_(1)
                     ms, vs = self._state_lists(ps)
@@ -267,10 +301,10 @@ class FusedAdam(_GradCoef, Optimizer):
                     aligned = same_layout(pdata, grads) and same_layout(pdata, ms) and same_layout(pdata, vs)
                     if dtype == torch.float32 and aligned and None not in (pflat, gflat, mflat, vflat):
                         C.adam_flat_(pflat, gflat, mflat, vflat, step, group["lr"], b1, b2, group["eps"],
-                                     group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef)
+                                     group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef, lr_dev)
                     else:
                         C.adam_multi_(pdata, grads, ms, vs, step, group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef)
+                                      group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef, lr_dev)
         return loss
 
     def state_dict(self):

@@ -6,6 +6,8 @@ reference's state_dict layout: rank 0 writes ``{"model", "optimizer", "epoch",
 every rank waits at a barrier, and resume restores the epoch so
 ``sampler.set_epoch`` continues the same permutation sequence. Files are
 written atomically (tmp + rename) and loaded with ``weights_only=True``.
+``lr_scheduler=`` (ops/lr_scheduler.py) adds its state under ``"lr_scheduler"``;
+a checkpoint without that key loads as before.
 """
 from __future__ import annotations
 
@@ -21,11 +23,13 @@ def _unwrap(sd: dict, prefix: str = "module.") -> dict:
 
 
 def save_checkpoint(path: str, model, optimizer=None, epoch: int = 0, rank: int = 0, extra: dict | None = None,
-                    barrier=None) -> None:
+                    barrier=None, lr_scheduler=None) -> None:
     if rank == 0:
         state = {"model": model.state_dict(), "epoch": int(epoch)}
         if optimizer is not None:
             state["optimizer"] = optimizer.state_dict()
+        if lr_scheduler is not None:
+            state["lr_scheduler"] = lr_scheduler.state_dict()
         if extra:
             state.update(extra)
         d = os.path.dirname(os.path.abspath(path))
@@ -37,7 +41,8 @@ def save_checkpoint(path: str, model, optimizer=None, epoch: int = 0, rank: int 
         barrier()
 
 
-def load_checkpoint(path: str, model=None, optimizer=None, map_location="cpu", strict: bool = True) -> dict:
+def load_checkpoint(path: str, model=None, optimizer=None, map_location="cpu", strict: bool = True,
+                    lr_scheduler=None) -> dict:
     state = torch.load(path, map_location=map_location, weights_only=True)
     if model is not None:
         sd = state["model"]
@@ -48,4 +53,6 @@ def load_checkpoint(path: str, model=None, optimizer=None, map_location="cpu", s
         model.load_state_dict(sd, strict=strict)
     if optimizer is not None and "optimizer" in state:
         optimizer.load_state_dict(state["optimizer"])
+    if lr_scheduler is not None and "lr_scheduler" in state:  # after the optimizer: it rewrites group["lr"]
+        lr_scheduler.load_state_dict(state["lr_scheduler"])
     return state

@@ -32,6 +32,9 @@ Extras: rank-0 snapshots every ``save_every`` epochs with resume
 layout, so snapshots interchange between engines), fault injection hooks,
 JSONL metrics. ``max_grad_norm=X`` clips the gradient norm between backward and
 step (ops/clip.py; autograd engine only, which ``engine="auto"`` then selects).
+``lr_scheduler=`` (ops/lr_scheduler.py: an instance bound to ``optimizer``, or a
+callable ``optimizer -> scheduler``) is stepped once per batch after
+``optimizer.step()`` and saved in snapshots; autograd engine only, as clipping.
 """
 from __future__ import annotations
 
@@ -90,7 +93,7 @@ class Trainer:
                  *, loss_fn=None, engine: str = "auto", graph: bool = True, comm=None,
                  snapshot_path: str | None = None, save_every: int = 0, metrics_path: str | None = None,
                  log=print, ddp_kwargs: dict | None = None, verbose: bool = True,
-                 max_grad_norm: float | None = None):
+                 max_grad_norm: float | None = None, lr_scheduler=None):
         self.gpu_id = env.local_rank() if gpu_id is None else gpu_id
         self.device = torch.device("cuda", self.gpu_id) if torch.cuda.is_available() else torch.device("cpu")
         self.rank = env.rank()
@@ -102,6 +105,7 @@ class Trainer:
         self.graph = graph
         self.max_grad_norm = max_grad_norm
         self._clipper = None
+        self.lr_scheduler = lr_scheduler  # resolved below, once the parameters are on their device
         self.snapshot_path = snapshot_path
         self.save_every = save_every
         self.epochs_run = 0
@@ -138,6 +142,8 @@ class Trainer:
             self.engine = None
             self.model = DistributedDataParallel(model, device_ids=[self.gpu_id] if self.device.type == "cuda" else None,
                                                  comm=self.comm, **(ddp_kwargs or {}))
+        if lr_scheduler is not None:
+            self.lr_scheduler = self._resolve_lr_scheduler(lr_scheduler)
         if snapshot_path and os.path.exists(snapshot_path):
             self._load_snapshot(snapshot_path)
 
@@ -164,6 +170,11 @@ class Trainer:
                 raise ValueError(f"{engine} engine does not clip gradients: max_grad_norm needs engine='autograd'")
             if engine == "auto":
                 return "autograd"
+        if self.lr_scheduler is not None:  # the fused / persistent engines take lr at plan time
+            if engine in ("fused", "persistent"):
+                raise ValueError(f"{engine} engine has a fixed learning rate: lr_scheduler needs engine='autograd'")
+            if engine == "auto":
+                return "autograd"
         if engine == "auto":
             return "persistent" if self._fusable(model) else "autograd"
         if engine in ("fused", "persistent") and not self._fusable(model):
@@ -188,7 +199,23 @@ class Trainer:
             if self.max_grad_norm is not None:
                 self._clip()
             self.optimizer.step()
+            if self.lr_scheduler is not None:
+                self.lr_scheduler.step()
         return loss
+
+    def _resolve_lr_scheduler(self, sched):
+        """An instance bound to the optimizer (its device buffers are placed again: the model has just
+        moved), or a callable ``optimizer -> scheduler``."""
+        from ..ops.lr_scheduler import LRScheduler
+
+        if isinstance(sched, LRScheduler):
+            if sched.optimizer is not self.optimizer:
+                raise ValueError("lr_scheduler is bound to another optimizer")
+            sched.rebind()
+            return sched
+        if callable(sched):
+            return sched(self.optimizer)
+        raise TypeError("lr_scheduler: a scheduler of ops.lr_scheduler or a callable optimizer -> scheduler")
 
     def _clip(self):
         """Clip between backward() and step(): fused into the update for FusedSGD / FusedAdam (p.grad
@@ -342,10 +369,11 @@ class Trainer:
         if self.engine is not None:  # torch.optim.SGD layout: snapshots interchange between engines
             self.engine.export_optimizer_state(self.optimizer)
         save_checkpoint(self.snapshot_path, self.model, self.optimizer, epoch=epoch, rank=self.rank,
-                        barrier=self.comm.barrier)
+                        barrier=self.comm.barrier, lr_scheduler=self.lr_scheduler)
 
     def _load_snapshot(self, path: str):
-        st = load_checkpoint(path, self.model, self.optimizer, map_location=self.device)
+        st = load_checkpoint(path, self.model, self.optimizer, map_location=self.device,
+                             lr_scheduler=self.lr_scheduler)
         if self.engine is not None:
             self.engine.import_optimizer_state(self.optimizer)
         self.epochs_run = int(st.get("epoch", -1)) + 1
