@@ -1,7 +1,7 @@
 // Host-side launch API of every gfx950 kernel in this framework.
 //
 // The kernels are compiled by hipcc without any torch headers (fast, torch-ABI
-// independent); csrc/bindings.cpp wraps them for at::Tensor. Every launcher
+// independent); csrc/bindings/ wraps them for at::Tensor. Every launcher
 // takes an explicit hipStream_t and never allocates, copies host<->device or
 // synchronises, so all of them can be captured into a hipGraph.
 #pragma once

@@ -49,7 +49,7 @@ def _torch_paths():
 def _sources():
     kernels = sorted((CSRC / "kernels").glob("*.hip"))
     hosts = [CSRC / "comm" / "rccl_comm.cpp", CSRC / "comm" / "xgmi_comm.cpp", CSRC / "reducer" / "reducer.cpp",
-             CSRC / "bindings.cpp"]
+             *sorted((CSRC / "bindings").glob("*.cpp"))]
     return kernels, hosts
 
 
