@@ -4,6 +4,7 @@
 
 #include "comm/xgmi_comm.h"
 #include "kernels/wave_loop_schedule.h"
+#include "kernels/wave_row_image.h"
 
 namespace ptdt {
 namespace {
@@ -102,9 +103,9 @@ class PersistentPlan {
                  double dampening, double weight_decay, bool nesterov, std::shared_ptr<XgmiComm> ar, int64_t W,
                  int64_t rank, int64_t num_samples, bool shuffle, int64_t seed, Tensor cursor, Tensor losses,
                  c10::optional<Tensor> stamps, int64_t variant, bool x_zero_padded, c10::optional<Tensor> idx,
-                 c10::optional<Tensor> lcache, int64_t idx_e0)
+                 c10::optional<Tensor> lcache, int64_t idx_e0, c10::optional<Tensor> row_image, int64_t row_image_kp)
       : keep_{X, P, G, cursor, losses}, ar_(ar), capacity_(losses.numel()), dev_(X.device().index()) {
-    for (const auto* t : {&Yf, &Yi, &mom, &opt_step, &stamps, &idx, &lcache})
+    for (const auto* t : {&Yf, &Yi, &mom, &opt_step, &stamps, &idx, &lcache, &row_image})
       if (has(*t)) keep_.push_back(**t);
     steps_per_epoch_ = (num_samples + B - 1) / B;
     TORCH_CHECK(X.is_cuda(), "X must be a GPU tensor");  // rows may be padded: checked below
@@ -190,6 +191,15 @@ class PersistentPlan {
       pa.lcache = lcache->data_ptr<int32_t>();
       pa.ltag = pa.lcache + 2 * stride;
     }
+    if (has(row_image)) {  // the dataset packed for the wave engine's lean kernels (wave_row_image.h)
+      TORCH_CHECK(row_image->is_cuda() && row_image->scalar_type() == at::kFloat && row_image->is_contiguous() &&
+                      row_image->device() == X.device() && row_image_kp > 0 && row_image_kp <= 64 &&
+                      row_image->numel() == N * wave_image_row_floats((int)row_image_kp),
+                  "persistent: row_image must be a contiguous f32 GPU tensor of N x 4 RS(row_image_kp) floats on X's device");
+      L_.image = row_image->data_ptr<float>();
+      L_.image_kp = (int)row_image_kp;
+      L_.image_rows = N;
+    }
     c10::hip::HIPGuard guard(dev_);
     const hipError_t e = fused_mlp_persistent_prepare(&L_);
     const PersistChoice& c = L_.choice;
@@ -229,6 +239,9 @@ class PersistentPlan {
   std::string kernel_variant() const {
     return L_.choice.engine == kEngWave ? wave_variant_name(L_.kernel_variant) : "";
   }
+  // bytes of the row image the plan's kernel gathers from; 0 when it reads X and Y (no image offered,
+  // or a kernel that does not take one)
+  int64_t image_bytes() const { return L_.uses_image ? wave_image_bytes(L_.image_rows, L_.image_kp) : 0; }
   ~PersistentPlan() {
     if (ev_) hipEventDestroy(ev_);
   }
@@ -444,19 +457,21 @@ void bind_engine(py::module_& m) {
                     c10::optional<Tensor>, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, bool, double, double,
                     double, double, bool, std::shared_ptr<XgmiComm>, int64_t, int64_t, int64_t, bool, int64_t, Tensor,
                     Tensor, c10::optional<Tensor>, int64_t, bool, c10::optional<Tensor>, c10::optional<Tensor>,
-                    int64_t>(),
+                    int64_t, c10::optional<Tensor>, int64_t>(),
            py::arg("X"), py::arg("Yf"), py::arg("Yi"), py::arg("P"), py::arg("G"), py::arg("mom"),
            py::arg("opt_step"), py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"), py::arg("loss_kind"),
            py::arg("ignore_index"), py::arg("has_bias"), py::arg("lr"), py::arg("momentum"), py::arg("dampening"),
            py::arg("weight_decay"), py::arg("nesterov"), py::arg("ar"), py::arg("W"), py::arg("rank"),
            py::arg("num_samples"), py::arg("shuffle"), py::arg("seed"), py::arg("cursor"), py::arg("losses"),
            py::arg("stamps") = py::none(), py::arg("variant") = 0, py::arg("x_zero_padded") = false,
-           py::arg("idx") = py::none(), py::arg("lcache") = py::none(), py::arg("idx_e0") = 0)
+           py::arg("idx") = py::none(), py::arg("lcache") = py::none(), py::arg("idx_e0") = 0,
+           py::arg("row_image") = py::none(), py::arg("row_image_kp") = 0)
       .def("launch", &PersistentPlan::launch, py::arg("n_steps"), py::arg("cursor_pos") = -1)
       .def("launch_at", &PersistentPlan::launch_at, py::arg("n_steps"), py::arg("pos"))
       .def_property_readonly("capacity", &PersistentPlan::capacity)
       .def_property_readonly("engine", &PersistentPlan::engine)
       .def_property_readonly("kernel_variant", &PersistentPlan::kernel_variant)
+      .def_property_readonly("image_bytes", &PersistentPlan::image_bytes)
       .def("set_timeline", &PersistentPlan::set_timeline, py::arg("addr"))
       .def("last_launch_ns", &PersistentPlan::last_launch_ns)
       .def("launch_wait_at", &PersistentPlan::launch_wait_at, py::arg("n_steps"), py::arg("pos"), py::arg("mode"),
@@ -480,7 +495,12 @@ void bind_engine(py::module_& m) {
   });
   py::class_<PersistChoice>(m, "PersistChoice")
       .def_property_readonly("name", &engine_name)
-      .def_readonly("x_width", &PersistChoice::x_width);
+      .def_readonly("x_width", &PersistChoice::x_width)
+      .def_readonly("kp", &PersistChoice::kp)
+      // the KP a row image must be packed for when the lean kernels of this choice gather from one, else 0
+      .def("image_kp", [](const PersistChoice& c, int64_t Dout, int64_t loss_kind) {
+        return linear_wave_reads_image(c, (int)Dout, (int)loss_kind) ? c.kp : 0;
+      }, py::arg("Dout"), py::arg("loss_kind"));
   m.def("persistent_choice", &persistent_choice, py::arg("B"), py::arg("Din"), py::arg("H"), py::arg("Dout"),
         py::arg("loss_kind"), py::arg("num_samples"), py::arg("world"), py::arg("variant") = 0,
         py::arg("has_bias") = true);
@@ -517,6 +537,48 @@ void bind_engine(py::module_& m) {
         return py::make_tuple(ofs, flags, slots, barriers, estride);
       },
       py::arg("S"), py::arg("B"), py::arg("e0"), py::arg("j0"), py::arg("n"), py::arg("depth") = kWavePrefetch);
+
+  // Row image of the wave engine (wave_row_image.h). wave_row_image_layout(Din, KP): (floats per
+  // record RS, bytes per row, slot of 1.0f or -1, slot of y, source[q][s] of every record slot: a
+  // feature index, or -1 for 1.0f, -2 for y, -3 for zero). wave_pack_rows packs X [N, Din] (rows may be
+  // padded) and Y [N] or [N, 1] into out [N, 4 RS] on the current stream.
+  m.def(
+      "wave_row_image_layout",
+      [](int Din, int KP) {
+        TORCH_CHECK(Din > 0 && KP > 0 && kWaveImageGroups * KP >= Din, "wave_row_image_layout: 4 KP must cover Din");
+        std::vector<std::vector<int>> src(kWaveImageGroups, std::vector<int>(wave_image_rs(KP)));
+        for (int q = 0; q < kWaveImageGroups; ++q)
+          for (int s = 0; s < wave_image_rs(KP); ++s) src[q][s] = wave_image_source(Din, KP, q, s);
+        return py::make_tuple(wave_image_rs(KP), wave_image_row_bytes(KP), wave_image_one_slot(KP), wave_image_y_slot(KP),
+                              src);
+      },
+      py::arg("Din"), py::arg("KP"));
+  m.def("wave_row_image_offset", [](int64_t row, int q, int KP) { return wave_image_offset(row, q, KP); }, py::arg("row"),
+        py::arg("q"), py::arg("KP"));
+  m.def("wave_row_image_fits", [](int64_t N, int Din, int KP) { return wave_image_fits(N, Din, KP); }, py::arg("N"),
+        py::arg("Din"), py::arg("KP"));
+  m.def(
+      "wave_pack_rows",
+      [](Tensor X, Tensor Y, int64_t Din, int64_t KP, Tensor out) {
+        TORCH_CHECK(X.is_cuda(), "X must be a GPU tensor");  // rows may be padded: checked below
+        check_gpu(Y, "Y");
+        check_gpu(out, "out");
+        const int64_t N = X.size(0);
+        TORCH_CHECK(X.scalar_type() == at::kFloat && Y.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat,
+                    "wave_pack_rows: f32 tensors");
+        TORCH_CHECK(X.dim() == 2 && X.size(1) == Din && X.stride(1) == 1 && X.stride(0) >= Din,
+                    "wave_pack_rows: X must be [N, Din] with unit column stride");
+        TORCH_CHECK(Y.numel() == N && Y.is_contiguous(), "wave_pack_rows: Y must hold one target per row");
+        TORCH_CHECK(wave_image_fits(N, (int)Din, (int)KP), "wave_pack_rows: the image exceeds the layout's limits");
+        TORCH_CHECK(out.is_contiguous() && out.numel() == N * wave_image_row_floats((int)KP) &&
+                        out.device() == X.device() && Y.device() == X.device(),
+                    "wave_pack_rows: out must be contiguous [N, 4 RS] on X's device");
+        c10::hip::HIPGuard guard(X.device().index());
+        hip_check(wave_pack_rows(X.data_ptr<float>(), X.stride(0), Y.data_ptr<float>(), N, (int)Din, (int)KP,
+                                 out.data_ptr<float>(), cur_stream(X)),
+                  "wave_pack_rows");
+      },
+      py::arg("X"), py::arg("Y"), py::arg("Din"), py::arg("KP"), py::arg("out"));
 
   // A HIP stream restricted to a set of CUs (hipExtStreamCreateWithCUMask), for
   // single-workgroup persistent engines: every launch lands on the same CU, so its

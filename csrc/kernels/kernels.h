@@ -161,6 +161,11 @@ enum WaveKernelVariant : int { kWaveGeneric = 0, kWaveLeanPlain = 1, kWaveLeanMo
 inline const char* wave_variant_name(int v) {
   return v == kWaveLeanPlain ? "lean-plain" : (v == kWaveLeanMom ? "lean-mom" : "generic");
 }
+// Configurations whose lean kernels gather from the dataset's row image (wave_row_image.h) instead of
+// X and Y: layout F, one output, float targets (MSE, soft-target CE).
+inline bool linear_wave_reads_image(const PersistChoice& c, int dout, int loss_kind) {
+  return c.engine == kEngWave && c.L == 0 && dout == 1 && loss_kind != kLossCEIndex;
+}
 // A persistent launch resolved once (engine choice, kernel, LDS size, argument
 // checks): relaunching it only sets n_steps (and the explicit-list cursor) and
 // calls hipLaunchKernel, so a short run pays no per-call planning.
@@ -173,7 +178,19 @@ struct PersistLaunch {
   PersistChoice choice{};       // what fused_mlp_persistent_prepare selected
   int kernel_variant = kWaveGeneric;  // WaveKernelVariant of fn (wave engine; kWaveGeneric elsewhere)
   int64_t host_ns[2] = {0, 0};  // CLOCK_MONOTONIC right before / after the last hipLaunchKernel
+  // Row image of the dataset (wave_row_image.h), offered by the plan's owner: image_kp is the KP it was
+  // packed for, image_rows its rows. linear_wave_prepare takes it (uses_image; a.X / a.ldx then describe
+  // the image) when it picks a lean kernel of a one-output float-target configuration -- those kernels
+  // read nothing else -- and falls back to the generic kernel without one.
+  const float* image = nullptr;
+  int image_kp = 0;
+  int64_t image_rows = 0;
+  bool uses_image = false;
 };
+// Packs the row image of X [n_rows, ldx] (Din features per row) and Y [n_rows] for KP features per
+// feature group into out [n_rows][4 RS] (wave_row_image.hip).
+hipError_t wave_pack_rows(const float* X, int64_t ldx, const float* Y, int64_t n_rows, int din, int kp, float* out,
+                          hipStream_t s);
 // Timeline probe support (timeline.hip): thread 0 of wave 0 writes the realtime counter.
 __device__ __forceinline__ void tl_mark(int64_t* tl, int k) {
   if (tl != nullptr && threadIdx.x == 0)

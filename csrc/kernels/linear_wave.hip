@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
+#include "wave_row_image.h"
 
 namespace ptdt {
 
@@ -138,6 +139,18 @@ hipError_t linear_wave_prepare(PersistLaunch* L) {
   const bool ar = a.ar.world > 1;
   L->kernel_variant = linear_wave_variant(a, L->p, c, a.mom != nullptr, L->p.stamps != nullptr);
   if (pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant) == nullptr) L->kernel_variant = kWaveGeneric;
+  // The lean kernels of one-output float-target configurations gather from the row image and from
+  // nothing else: without a matching image the plan runs the generic kernel on X and Y.
+  L->uses_image = false;
+  if (L->kernel_variant != kWaveGeneric && linear_wave_reads_image(c, a.Dout, a.loss_kind)) {
+    if (L->image != nullptr && L->image_kp == c.kp && L->image_rows == L->p.N && wave_image_fits(L->p.N, a.Din, c.kp)) {
+      L->a.X = L->image;
+      L->a.ldx = wave_image_row_floats(c.kp);
+      L->uses_image = true;
+    } else {
+      L->kernel_variant = kWaveGeneric;
+    }
+  }
   return persist_set_kernel(L, pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant), kThreads, lds);
 }
 

@@ -38,6 +38,7 @@
 #include "kernels.h"
 #include "sampler.h"
 #include "wave_loop_schedule.h"
+#include "wave_row_image.h"
 
 namespace ptdt {
 namespace lw {
@@ -502,8 +503,17 @@ __device__ __forceinline__ bool ll_exchange_pair(const XgmiArgs& x, uint32_t seq
   return ok;
 }
 
-template <int R, int KP, int DOUT, int RY>
-struct Batch {
+// Row-image kernels (layout F): the lane's record of each of its R rows as it was loaded, NV whole
+// 16-byte vectors (a base of their Batch; the other kernels' Batch has an empty base and its old layout)
+template <int R, int KP>
+struct RowRecords {
+  typedef float rec4 __attribute__((ext_vector_type(4)));
+  static constexpr int NV = (wave_image_used(KP) + 3) / 4;
+  rec4 img[R][NV];
+};
+struct NoRecords {};
+template <int R, int KP, int DOUT, int RY, bool IMG = false>
+struct Batch : std::conditional_t<IMG, RowRecords<R, KP>, NoRecords> {
   float x[R][KP];
   float y[RY][DOUT];
   int yi[RY];
@@ -1089,6 +1099,13 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // DOUT == 1: reduce-scatter, one row per lane (rows q & (R-1)); else every lane all rows
   constexpr bool SCATTER = DOUT == 1 && R > 1;
   constexpr int RY = SCATTER ? 1 : R;  // target rows a lane loads / computes the loss of
+  // IMG: the lean kernels of one-output float-target configurations gather from the dataset's row image
+  // (wave_row_image.h; the host hands it over as X with ldx = its row floats, linear_wave_prepare): a
+  // lane's record holds its KP features, 1.0f behind an odd KP and the row's target -- whole 16-byte
+  // loads, no target gather, no list entry of the own row.
+  constexpr bool IMG = LEAN && DOUT == 1 && LOSS != kLossCEIndex;
+  constexpr bool PKT = IMG && (KP & 1) != 0;  // packed backward tail {x[KP-1], 1} . {g, g}
+  using BatchT = Batch<R, KP, DOUT, RY, IMG>;
   extern __shared__ int elist[];
   // The kernel arguments the prologue reads are loaded here in one batch, pinned by the empty asm
   // (one wait for all), before the first branch. Left to the compiler, each scalar load followed
@@ -1197,6 +1214,12 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   const uint32_t n_rows = (uint32_t)n_rows_arg;
   const __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(X_arg, n_rows * (uint32_t)ldx * 4u);
   const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(Y_arg, n_rows * (LOSS == kLossCEIndex ? 8u : (uint32_t)(DOUT * 4)));
+  // The image kernels read no targets, but they keep the target pointer's kernel-argument load where the
+  // other kernels have it (the second scalar batch of the prologue). Measured, not derived: without this
+  // line the warm timeline's prologue read 1.56-1.60 us against the parent's 1.52-1.56 in nine blocks
+  // each, with it 1.52-1.56 (profiles/wave_row_image.md section 4); the instructions in front of
+  // the barrier are otherwise the same, and a build with the packed SGD alone showed the higher reading too.
+  if constexpr (IMG) asm volatile("" ::"s"(Y_arg));
   const uint32_t ldx4 = (uint32_t)ldx * 4u, k04 = (uint32_t)k0 * 4u;
   // loss scales of a full batch and of the one short last batch (nb_last == B if none); each batch
   // carries its pair, selected at fetch time (off the step's dependent chain). Lean: no short batch,
@@ -1205,10 +1228,23 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   const float inv_full = 1.f / (float)((LOSS == kLossMSE) ? B * DOUT : B);
   const float inv_last = 1.f / (float)((LOSS == kLossMSE) ? nb_last * DOUT : nb_last);
   const float gs_full = grad_scale_arg * inv_full, gs_last = grad_scale_arg * inv_last;
-  auto load_batch = [&](Batch<R, KP, DOUT, RY>& f, const int (&sel)[R], int sel_y, int nb) {
+  const uint32_t rec4 = (uint32_t)q * (uint32_t)(wave_image_rs(KP) * 4);  // IMG: this lane's record in a row
+  const bool own_b0 = (q & 1) != 0, own_b1 = (q & 2) != 0;                 // IMG: bits of rho_own
+  auto load_batch = [&](BatchT& f, const int (&sel)[R], int sel_y, int nb) {
     f.nb = nb;
     f.cg = nb == B ? gs_full : gs_last;
     f.cl = nb == B ? inv_full : inv_last;
+    if constexpr (IMG) {
+      using BT = RowRecords<R, KP>;
+#pragma unroll
+      for (int rho = 0; rho < R; ++rho) {  // whole 16-byte loads: a record is a whole number of them
+        const uint32_t off = __umul24((uint32_t)sel[rho], ldx4) + rec4;
+#pragma unroll
+        for (int v = 0; v < BT::NV; ++v)
+          f.img[rho][v] = __builtin_bit_cast(typename BT::rec4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off + 16 * v, 0, 0));
+      }
+      return;
+    }
 #pragma unroll
     for (int rho = 0; rho < R; ++rho) buffer_load_chunk<KP>(xrs, __umul24((uint32_t)sel[rho], ldx4) + k04, f.x[rho]);
 #pragma unroll
@@ -1223,7 +1259,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
     }
   };
-  Batch<R, KP, DOUT, RY> buf[kNB];
+  BatchT buf[kNB];
   const ListCache lc{pa.lcache, pa.ltag, al4(ns_arg)};  // the global cache keeps the unpadded stride
   rank_epoch_indices_or(given_list(pa, e0), list(e0), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples, pa.seed, e0, pa.shuffle,
                      (int)threadIdx.x, kThreads, lc);
@@ -1350,7 +1386,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       bar_due = barriers < T;
     }
   };
-  auto fetch = [&](Batch<R, KP, DOUT, RY>& f) {
+  auto fetch = [&](BatchT& f) {
     load_batch(f, sel_next, sel_y_next, nb_next);
     read_index();
   };
@@ -1368,9 +1404,9 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   auto read_run = [&]() {
 #pragma unroll
     for (int rho = 0; rho < R; ++rho) sel_next[rho] = lp[rho * 16];
-    if constexpr (SCATTER) sel_y_next = lp_y[0];
+    if constexpr (SCATTER && !IMG) sel_y_next = lp_y[0];
     lp += B;
-    lp_y += B;
+    if constexpr (!IMG) lp_y += B;
   };
   auto read_checked = [&]() {
     bool bar, switched;
@@ -1458,12 +1494,39 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   }
   int rslot = 0;  // loss ring slot of the next step
   const float lr_b = hb ? lr : 0.f;  // plain SGD's bias step
-  auto train = [&](Batch<R, KP, DOUT, RY>& f, int step, auto sgd_tag, auto ring_tag) {
+  auto train = [&](BatchT& f, int step, auto sgd_tag, auto ring_tag) {
     constexpr int SGD = decltype(sgd_tag)::value;
     constexpr bool MOM = SGD == kSgdMom;
     constexpr bool RING = decltype(ring_tag)::value;
     const int nb = f.nb;
-    if constexpr (LEAN) {
+    float one[R], ximg[R][KP], yimg = 0.f;  // IMG: the record's 1.0f (odd KP), features, the own row's target
+    if constexpr (IMG) {
+      // One wait for the batch, as below, with the pins on the loaded vectors as a whole (last load
+      // first): pinned element by element, the compiler narrows the loads to the elements used and
+      // moves the pieces through scratch. Then the record's fields by name.
+      using BT = RowRecords<R, KP>;
+      float ypk[R];
+#pragma unroll
+      for (int rho = R - 1; rho >= 0; --rho) {
+#pragma unroll
+        for (int v = BT::NV - 1; v >= 0; --v) asm volatile("" : "+v"(f.img[rho][v]));
+      }
+#pragma unroll
+      for (int rho = 0; rho < R; ++rho) {
+#pragma unroll
+        for (int k = 0; k < KP; ++k) ximg[rho][k] = f.img[rho][k >> 2][k & 3];
+        one[rho] = PKT ? f.img[rho][KP >> 2][KP & 3] : 1.f;
+        ypk[rho] = f.img[rho][wave_image_y_slot(KP) >> 2][wave_image_y_slot(KP) & 3];
+      }
+      // the own row's target, chosen from the R loaded ones by rho_own (lane-constant masks)
+      float y = ypk[0];
+      if constexpr (R == 2) y = own_b0 ? ypk[1] : ypk[0];
+      if constexpr (R == 4) {
+        const float y01 = own_b0 ? ypk[1] : ypk[0], y23 = own_b0 ? ypk[3] : ypk[2];
+        y = own_b1 ? y23 : y01;
+      }
+      yimg = y;
+    } else if constexpr (LEAN) {
       // The batch was requested kNB steps ago: one wait for all of it here. Every loaded register
       // passes through an empty asm, so the compiler places its wait for the batch's last load in
       // front of the first one and none later (it had one in front of each load's first use).
@@ -1480,12 +1543,13 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         for (int k = KP - 1; k >= 0; --k) asm volatile("" : "+v"(f.x[rho][k]));
       }
     }
+    const float (&x)[R][KP] = *(IMG ? &ximg : &f.x);
     // ---- forward: partial logits of this feature group
     float zp[R][DOUT];
 #pragma unroll
     for (int rho = 0; rho < R; ++rho) {
 #pragma unroll
-      for (int c = 0; c < DOUT; ++c) zp[rho][c] = chunk_dot<KP>(f.x[rho], W[c]);
+      for (int c = 0; c < DOUT; ++c) zp[rho][c] = chunk_dot<KP>(x[rho], W[c]);
     }
     tk.tick(1);
     // ---- logits -> loss -> dL/dz (g[rho][c] in every lane)
@@ -1501,7 +1565,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
       z += Wb[0];
       float gz, l, cnt;
-      row_loss(&z, f.y[0], f.yi[0], LEAN || rho_own * 16 + i < nb, &gz, l, cnt);
+      row_loss(&z, IMG ? &yimg : f.y[0], f.yi[0], LEAN || rho_own * 16 + i < nb, &gz, l, cnt);
       // each batch row counted once: R == 2 has every row in two DPP rows
       const bool owner = R == 4 || q < 2;
       lraw = l;
@@ -1530,7 +1594,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
 #pragma unroll
         for (int c = 0; c < DOUT; ++c) z[c] = allrows(zp[rho][c]) + Wb[c];
         float l, cnt;
-        row_loss(z, f.y[rho], f.yi[rho], LEAN || rho * 16 + i < nb, g[rho], l, cnt);
+        row_loss(z, IMG ? &yimg : f.y[rho], f.yi[rho], LEAN || rho * 16 + i < nb, g[rho], l, cnt);
         lsum += l;
         csum += cnt;
       }
@@ -1558,22 +1622,34 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       float t[KP];
 #pragma unroll
       for (int k = 0; k + 1 < KP; k += 2) {
-        f2v tv = f2v{f.x[0][k], f.x[0][k + 1]} * f2v{g[0][c], g[0][c]};
+        f2v tv = f2v{x[0][k], x[0][k + 1]} * f2v{g[0][c], g[0][c]};
 #pragma unroll
         for (int rho = 1; rho < R; ++rho)
-          tv = __builtin_elementwise_fma(f2v{f.x[rho][k], f.x[rho][k + 1]}, f2v{g[rho][c], g[rho][c]}, tv);
+          tv = __builtin_elementwise_fma(f2v{x[rho][k], x[rho][k + 1]}, f2v{g[rho][c], g[rho][c]}, tv);
         t[k] = tv.x;
         t[k + 1] = tv.y;
       }
-      if constexpr ((KP & 1) != 0) {
-        float tl = g[0][c] * f.x[0][KP - 1];
+      float tbp = 0.f;
+      if constexpr (PKT) {
+        // odd KP with the row image: {x[KP-1], 1} . {g, g} gives the last feature's sum and the bias sum
+        // in one packed multiply and R - 1 packed FMAs. g * 1 is g and fma(g, 1, s) is the rounded
+        // s + g: the bits of the scalar sum below.
+        f2v tv = f2v{x[0][KP - 1], one[0]} * f2v{g[0][c], g[0][c]};
 #pragma unroll
-        for (int rho = 1; rho < R; ++rho) tl = fmaf(g[rho][c], f.x[rho][KP - 1], tl);
+        for (int rho = 1; rho < R; ++rho)
+          tv = __builtin_elementwise_fma(f2v{x[rho][KP - 1], one[rho]}, f2v{g[rho][c], g[rho][c]}, tv);
+        t[KP - 1] = tv.x;
+        tbp = tv.y;
+      } else if constexpr ((KP & 1) != 0) {
+        float tl = g[0][c] * x[0][KP - 1];
+#pragma unroll
+        for (int rho = 1; rho < R; ++rho) tl = fmaf(g[rho][c], x[rho][KP - 1], tl);
         t[KP - 1] = tl;
       }
       float tb = g[0][c];
 #pragma unroll
       for (int rho = 1; rho < R; ++rho) tb += g[rho][c];
+      if constexpr (PKT) tb = tbp;
       // the KP weight sums and the bias sum of class c: one row16_sum_n group
       float sums[KP + 1];
 #pragma unroll
@@ -1638,6 +1714,32 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     };
 #pragma unroll
     for (int c = 0; c < DOUT; ++c) {
+      if constexpr (VAR == kWaveLeanPlain) {
+        // lean plain SGD, packed: [W[c][0 .. KP-1], Wb[c]] updated in pairs, one v_pk_fma_f32 per pair
+        // (5.6 cycles of issue against 10-12 for two v_fma_f32, tools/microbench_isa.hip) with the constant pair
+        // {-lr, -lr} ({-lr, -lr_b} where the bias is the second half); an odd last value stays
+        // scalar. Each half is the scalar update's fma(-lr, g, w): the same bits.
+        float u[KP + 1], gr[KP + 1];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          u[k] = W[c][k];
+          gr[k] = gW[c][k];
+        }
+        u[KP] = Wb[c];
+        gr[KP] = gb[c];
+#pragma unroll
+        for (int k = 0; k + 1 < KP + 1; k += 2) {
+          const f2v nl = {-lr, k + 1 == KP ? -lr_b : -lr};
+          const f2v r = __builtin_elementwise_fma(nl, f2v{gr[k], gr[k + 1]}, f2v{u[k], u[k + 1]});
+          u[k] = r.x;
+          u[k + 1] = r.y;
+        }
+        if constexpr ((KP & 1) == 0) u[KP] = fmaf(-lr_b, gr[KP], u[KP]);
+#pragma unroll
+        for (int k = 0; k < KP; ++k) W[c][k] = u[k];
+        Wb[c] = u[KP];
+        continue;
+      }
 #pragma unroll
       for (int k = 0; k < KP; ++k) upd(W[c][k], M[c][k], gW[c][k]);
       if constexpr (SGD == kSgdPlain) {

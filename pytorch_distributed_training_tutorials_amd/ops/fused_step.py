@@ -206,6 +206,7 @@ class FusedMLPStep:
             raise RuntimeError("the persistent engine needs the xGMI all-reduce for world > 1")
         ce_index = self.loss_kind == LOSS_KINDS["ce_index"]
         vid = self._vid(variant)
+        image, image_kp = self._wave_image(X, Y, batch_size, sampler, vid, stamps is not None)
         X, padded = self._wave_input(X, batch_size, sampler, vid)
         self._pending = False
         return self._C.PersistentPlan(
@@ -214,7 +215,7 @@ class FusedMLPStep:
             self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov,
             self.xgmi.handle if self.xgmi is not None else None, sampler.num_replicas, sampler.rank,
             sampler.num_samples, sampler.shuffle, sampler.seed, cursor, losses, stamps, vid, padded, idx, lcache,
-            idx_e0)
+            idx_e0, image, image_kp)
 
     def _vid(self, variant: str | None) -> int:
         """Engine variant id; dtype="bf16" means the bf16 TP engine (and nothing else)."""
@@ -236,12 +237,55 @@ class FusedMLPStep:
             return X, False
         key = (X.data_ptr(), X._version, tuple(X.shape), width)
         cached = getattr(self, "_xpad", None)
-        if cached is None or cached[0] != key:
+        if cached is None or cached[0] != key or cached[2] is not X:  # the entry keeps X: see _wave_image
             xp = torch.zeros(X.shape[0], width, device=X.device, dtype=X.dtype)
             xp[:, :self.Din].copy_(X)
-            cached = (key, xp[:, :self.Din])
+            cached = (key, xp[:, :self.Din], X)
             self._xpad = cached
         return cached[1], True
+
+    def _wave_image(self, X, Y, batch_size, sampler, vid, stamps=False):
+        """The row image (csrc/kernels/wave_row_image.h) the wave engine's lean kernels of one-output,
+        float-target configurations gather from: every dataset row as four records of features, 1.0
+        behind an odd feature count and the row's target. Built by the native pack kernel and owned by
+        this engine, one image cached per (X, Y) version and layout: a plan snapshots the dataset when
+        it is created, as it does with the zero-padded copy of ``_wave_input``. Returns ``(None, 0)``
+        when the configuration takes no image, or when the image would exceed
+        ``$PTDT_WAVE_IMAGE_MAX_MB`` (default 256) or the layout's limits: the plan then runs the
+        generic kernel on X and Y, about 10 % slower per step than a lean kernel (there is no lean
+        kernel without an image for these configurations).
+
+        The cache entry holds X and Y themselves (so their storage cannot be recycled under the key):
+        the engine keeps the last dataset, its image and, for Din < 4 KP, the zero-padded copy of
+        ``_wave_input`` alive for its own lifetime. The padded copy is still built next to the image:
+        the layout selection accepts Din < 4 KP only for padded rows, and the generic fall-back reads it."""
+        choice = self._C.persistent_choice(batch_size, self.Din, self.H, self.Dout, self.loss_kind,
+                                           sampler.num_samples, sampler.num_replicas, vid, self.has_bias)
+        kp = choice.image_kp(self.Dout, self.loss_kind)
+        if kp == 0 or X.dim() != 2 or X.stride(1) != 1 or X.dtype != torch.float32 or Y.dtype != torch.float32:
+            return None, 0
+        lean = self._C.persistent_kernel_variant(batch_size, self.Din, self.H, self.Dout, self.loss_kind,
+                                                 sampler.num_samples, sampler.num_replicas, vid, self.has_bias,
+                                                 self.momentum if self.mom is not None else 0.0, self.weight_decay,
+                                                 stamps)
+        if lean == "generic":  # only the lean kernels gather from an image
+            return None, 0
+        n = X.shape[0]
+        if Y.numel() != n or not self._C.wave_row_image_fits(n, self.Din, kp):
+            return None, 0
+        rs, row_bytes = self._C.wave_row_image_layout(self.Din, kp)[:2]
+        if n * row_bytes > float(os.environ.get("PTDT_WAVE_IMAGE_MAX_MB", "256")) * 2 ** 20:
+            return None, 0
+        key = (X.data_ptr(), X._version, tuple(X.shape), tuple(X.stride()), Y.data_ptr(), Y._version, tuple(Y.shape), kp)
+        # The entry keeps X and Y themselves: while it lives, their storage cannot be freed and handed to
+        # another tensor that would then match the key with other data behind it.
+        cached = getattr(self, "_ximage", None)
+        if cached is None or cached[0] != key or cached[2] is not X or cached[3] is not Y:
+            image = torch.empty(n, 4 * rs, device=X.device, dtype=torch.float32)
+            self._C.wave_pack_rows(X, Y.contiguous(), self.Din, kp, image)
+            cached = (key, image, X, Y)
+            self._ximage = cached
+        return cached[1], kp
 
     def persistent_engine(self, batch_size: int, sampler, variant: str | None = None) -> str:
         """Which persistent engine :meth:`run_persistent` runs: "workgroup" or
