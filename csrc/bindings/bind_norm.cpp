@@ -36,6 +36,8 @@ void bn_rows(const Tensor& x, int64_t* M, int* C) {
   *M = x.numel() / std::max<int64_t>(*C, 1);
   const int V = x.scalar_type() == at::kFloat ? 4 : 8;
   TORCH_CHECK(*C % V == 0, "batchnorm: channels must be a multiple of ", V);
+  TORCH_CHECK(*C <= bn_max_channels(), "batchnorm: at most ", bn_max_channels(),
+              " channels (the per-channel tables of the elementwise passes live in LDS)");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "batchnorm: 16-byte aligned data expected");
 }
 
@@ -311,6 +313,10 @@ std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, c10::optional<Tensor> y, c10::op
                            bool relu, bool want_dres, bool want_dweight, c10::optional<Tensor> tickets,
                            c10::optional<Tensor> dweight_out, c10::optional<Tensor> dbias_out,
                            c10::optional<Tensor> dy2, c10::optional<Tensor> mask) {
+  // a residual gradient means the forward added a residual, and then x alone does not give the
+  // ReLU mask: only the forward's y or its mask bytes do
+  TORCH_CHECK(!(relu && want_dres) || has(y) || has(mask),
+              "batchnorm: bn_bwd with relu and want_dres needs the forward's y or mask");
   BnBwdCall c(dy, x, y, weight, stats, relu, want_dres, want_dweight, tickets, dweight_out, dbias_out, dy2, mask,
               /*reduce_only=*/false, /*with_coef=*/true);
   hip_check(bn_backward(c.a, cur_stream(x)), "bn_backward");
@@ -508,7 +514,8 @@ Tensor maxpool2d_bwd(Tensor gy, Tensor arg, std::vector<int64_t> in_size, std::v
                      std::vector<int64_t> st, std::vector<int64_t> pad) {
   TORCH_CHECK(in_size.size() == 4, "maxpool: input size [N, C, H, W]");
   TORCH_CHECK(gy.is_cuda() && gy.dim() == 4 && gy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  arg.sizes() == gy.sizes() && arg.strides() == gy.strides() && arg.scalar_type() == at::kByte,
+                  arg.sizes() == gy.sizes() && arg.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  arg.device() == gy.device() && arg.scalar_type() == at::kByte,
               "maxpool backward: gy / argmax must be matching channels_last tensors");
   Tensor gx = at::empty(in_size, gy.options().memory_format(at::MemoryFormat::ChannelsLast));
   PoolArgs a = pool_args(gx, gy.size(2), gy.size(3), k, st, pad);
@@ -526,6 +533,14 @@ void bind_norm(py::module_& m) {
   m.def("conv1x1_bwd", &conv1x1_bwd_, "fused BN-apply + 1x1 conv data and weight gradients (bf16)");
   m.def("conv1x1_bwd_supported", &conv1x1_bwd_supported_);
   m.def("bn_relu", &bn_relu);
+  m.def("bn_max_channels", &bn_max_channels, "widest channel count the NHWC BatchNorm kernels take");
+  m.def("bn_geometry", [](int64_t M, int64_t C, bool f32) {
+    int g[4];
+    bn_geometry(M, (int)C, f32 ? kF32 : kBF16, g);
+    return py::make_tuple(g[0], g[1], g[2], g[3], bn_workspace_floats(M, (int)C, f32 ? kF32 : kBF16),
+                          bn_num_tickets((int)C, f32 ? kF32 : kBF16));
+  }, "reduction launch geometry of an [M, C] tensor: (TC, RPI, gx, gy, workspace floats, tickets)", py::arg("M"),
+        py::arg("C"), py::arg("f32"));
   m.def("bn_fwd_train", &bn_fwd_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("num_batches_tracked"), py::arg("residual"), py::arg("relu"),
         py::arg("momentum"), py::arg("eps"), py::arg("tickets") = py::none(), py::arg("want_mask") = false,

@@ -21,7 +21,7 @@
 // re-arms its ticket. So a BN forward is 2 launches (stats, apply) and a
 // backward 2 launches (reduce, apply).
 //
-// Forward statistics use shifted sums (x - K, K = row 0 of the channel), so
+// Forward statistics use shifted sums (x - K, K = the channel's median of rows 0, M/2, M-1), so
 // E[(x-K)^2] - E[x-K]^2 does not cancel catastrophically for |mean| >> std;
 // the final combine runs in double. Running stats: torch's momentum update
 // with the unbiased variance, num_batches_tracked incremented in-kernel.
@@ -189,9 +189,11 @@ __device__ __forceinline__ void block_rows_sum(float (&acc)[NS][V], float* sh, i
   if (tid < width) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      float a = 0.f;
-      for (int r = 0; r < RPI; ++r) a += sh[(s * RPI + r) * width + tid];
-      out[s] = a;
+      // in double: a serial float sum of up to 512 row sums was the largest error of the whole
+      // reduction (several ulp of the variance, measured against float64)
+      double a = 0.0;
+      for (int r = 0; r < RPI; ++r) a += (double)sh[(s * RPI + r) * width + tid];
+      out[s] = (float)a;
     }
   }
 }
@@ -336,6 +338,17 @@ struct BnSyncBwdParams : BnBwdParams {
   double* sums;  // [2, C]: local sum g, sum g (x - mean) about the GLOBAL mean
 };
 
+// Pivot K of the shifted sums: per channel the median of rows 0, M/2 and M-1, so one outlying row
+// (row 0 of a padded or sorted batch) cannot put K far from the mean and bring the cancellation in
+// E[(x-K)^2] - E[x-K]^2 back. Every block and the last block's combine form the same K.
+__device__ __forceinline__ float median3(float a, float b, float c) {
+  return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+}
+template <typename T>
+__device__ __forceinline__ float pivot_of(const T* x, int64_t M, int C, int c) {
+  return median3(Cvt<T>::load(x, c), Cvt<T>::load(x, (M / 2) * C + c), Cvt<T>::load(x, (M - 1) * C + c));
+}
+
 template <typename T, bool SYNC = false>
 __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x, int64_t M, int C, int TC, int RPI,
                                                         int64_t rows_per_block, int il, float* ws, int* tickets,
@@ -361,21 +374,36 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
 #pragma unroll
   for (int v = 0; v < V; ++v) acc[0][v] = acc[1][v] = 0.f;
   if (active) {
-    float K[V];
-    VecIO<T>::load(x + c0, K);  // pivot: row 0 (same for every block)
+    float K[V], K1[V], K2[V];  // pivot (same for every block): pivot_of(), a vector at a time
+    VecIO<T>::load(x + c0, K);
+    VecIO<T>::load(x + (M / 2) * C + c0, K1);
+    VecIO<T>::load(x + (M - 1) * C + c0, K2);
+#pragma unroll
+    for (int v = 0; v < V; ++v) K[v] = median3(K[v], K1[v], K2[v]);
     int64_t r = rb + rr;
     for (; r + (U - 1) * rs < re; r += U * rs) {  // U independent 16-B loads in flight
       float a[U][V];
 #pragma unroll
       for (int u = 0; u < U; ++u) VecIO<T>::load(x + row(r + u * rs) * C + c0, a[u]);
+      // each batch of U rows is summed on its own and then added: a running float sum of every
+      // row stagnates on bf16 data (the addends sit on a coarse grid and tie after tie rounds to
+      // even, i.e. down), which biased the variance low by up to 2e-6 of itself on tall tensors
+      float b[2][V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) b[0][v] = b[1][v] = 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int v = 0; v < V; ++v) {
           const float d = a[u][v] - K[v];
-          acc[0][v] += d;
-          acc[1][v] = fmaf(d, d, acc[1][v]);
+          b[0][v] += d;
+          b[1][v] = fmaf(d, d, b[1][v]);
         }
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        acc[0][v] += b[0][v];
+        acc[1][v] += b[1][v];
+      }
     }
     for (; r < re; r += rs) {
       float a[V];
@@ -403,7 +431,7 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
     if (tid < width && c < C) {
       double m2 = q - s * s / (double)M;
       if (m2 < 0.0) m2 = 0.0;
-      p.rec[c] = (double)Cvt<T>::load(x, c) + s / (double)M;
+      p.rec[c] = (double)pivot_of<T>(x, M, C, c) + s / (double)M;
       p.rec[C + c] = m2;
     }
     if (tid == 0) {
@@ -413,7 +441,7 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
     return;
   }
   if (tid < width && c < C) {
-    const double Kc = (double)Cvt<T>::load(x, c);
+    const double Kc = (double)pivot_of<T>(x, M, C, c);
     const double ms = s / (double)M;
     double var = q / (double)M - ms * ms;
     if (var < 0.0) var = 0.0;
@@ -810,15 +838,29 @@ int pass_dirs() {
 }
 int dir(int bit) { return (pass_dirs() & bit) ? 1 : 0; }
 
+// Dynamic LDS of the elementwise passes: their per-channel tables (2, 3 or 5 floats per channel).
+// Above 64 KiB a kernel has to be opted in to its size; a workgroup can hold 160 KiB at the most, and
+// the widest table (5 floats: bn_bwd_apply_kernel<MASK 2>) then bounds the channel count the native
+// path takes (bn_max_channels(); the bindings and ops/norm.py send wider tensors to the composite).
+constexpr size_t kLdsOptIn = 64 * 1024, kLdsMax = 160 * 1024;
+template <typename K, typename... A>
+hipError_t launch_lds(K kernel, dim3 grid, dim3 blk, size_t lds, hipStream_t s, A... args) {
+  if (lds > kLdsMax) return hipErrorInvalidValue;
+  if (lds > kLdsOptIn)
+    PTDT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, blk, lds, s, args...);
+  return hipGetLastError();
+}
+
 // runtime AU -> template
 template <typename F>
 hipError_t with_au(F&& f) {
   switch (apply_unroll()) {
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    default: f(std::integral_constant<int, 1>{}); break;
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 1>{});
   }
-  return hipGetLastError();
 }
 
 template <typename T>
@@ -846,12 +888,12 @@ hipError_t fwd_impl(const BnFwdArgs& a, hipStream_t s) {
   return with_au([&](auto au) {
     constexpr int AU = decltype(au)::value;
     if (a.relu) {
-      if (r && mo) hipLaunchKernelGGL((bn_apply_kernel<T, true, true, true, AU>), grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), mo);
-      else if (r) hipLaunchKernelGGL((bn_apply_kernel<T, true, true, false, AU>), grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
-      else hipLaunchKernelGGL((bn_apply_kernel<T, true, false, false, AU>), grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
+      if (r && mo) return launch_lds(bn_apply_kernel<T, true, true, true, AU>, grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), mo);
+      else if (r) return launch_lds(bn_apply_kernel<T, true, true, false, AU>, grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
+      else return launch_lds(bn_apply_kernel<T, true, false, false, AU>, grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
     } else {
-      if (r) hipLaunchKernelGGL((bn_apply_kernel<T, false, true, false, AU>), grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
-      else hipLaunchKernelGGL((bn_apply_kernel<T, false, false, false, AU>), grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
+      if (r) return launch_lds(bn_apply_kernel<T, false, true, false, AU>, grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
+      else return launch_lds(bn_apply_kernel<T, false, false, false, AU>, grid, blk, sh_ap, s, x, r, y, sc, sf, nvec, C, dir(2), nullptr);
     }
   });
 }
@@ -870,11 +912,11 @@ hipError_t apply_impl(const void* x, const void* res, void* y, const float* scal
   return with_au([&](auto au) {
     constexpr int AU = decltype(au)::value;
     if (relu) {
-      if (r) hipLaunchKernelGGL((bn_apply_kernel<T, true, true, false, AU>), grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
-      else hipLaunchKernelGGL((bn_apply_kernel<T, true, false, false, AU>), grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
+      if (r) return launch_lds(bn_apply_kernel<T, true, true, false, AU>, grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
+      else return launch_lds(bn_apply_kernel<T, true, false, false, AU>, grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
     } else {
-      if (r) hipLaunchKernelGGL((bn_apply_kernel<T, false, true, false, AU>), grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
-      else hipLaunchKernelGGL((bn_apply_kernel<T, false, false, false, AU>), grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
+      if (r) return launch_lds(bn_apply_kernel<T, false, true, false, AU>, grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
+      else return launch_lds(bn_apply_kernel<T, false, false, false, AU>, grid, blk, sh_ap, s, xx, r, yy, scale, shift, nvec, C, 0, nullptr);
     }
   });
 }
@@ -904,8 +946,8 @@ hipError_t bwd_launch(const BnBwdArgs& a, const Geom& g, hipStream_t s) {
                        a.tickets, a.p);
     PTDT_HIP_CHECK(hipGetLastError());
     return with_au([&](auto au) {
-      hipLaunchKernelGGL((bn_bwd_apply_g_kernel<T, decltype(au)::value>), grid, blk, (size_t)3 * a.C * sizeof(float),
-                         s, static_cast<const T*>(dr), x, dx, a.p, nvec, a.C, dir(8));
+      return launch_lds(bn_bwd_apply_g_kernel<T, decltype(au)::value>, grid, blk, (size_t)3 * a.C * sizeof(float), s,
+                        static_cast<const T*>(dr), x, dx, a.p, nvec, a.C, dir(8));
     });
   }
   hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, MASK, ADD2>), dim3(g.gx, g.gy), dim3(kRed), sh_red, s, dy, dy2, x, y,
@@ -917,8 +959,8 @@ hipError_t bwd_launch(const BnBwdArgs& a, const Geom& g, hipStream_t s) {
   } else {
     const size_t sh_ap = (size_t)(MASK == 2 ? 5 : 3) * a.C * sizeof(float);
     return with_au([&](auto au) {
-      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK, false, ADD2, decltype(au)::value>), grid, blk, sh_ap, s, dy,
-                         dy2, x, y, dx, dr, a.p, nvec, a.C, dir(8));
+      return launch_lds(bn_bwd_apply_kernel<T, MASK, false, ADD2, decltype(au)::value>, grid, blk, sh_ap, s, dy, dy2,
+                        x, y, dx, dr, a.p, nvec, a.C, dir(8));
     });
   }
 }
@@ -993,8 +1035,8 @@ hipError_t apply_g_impl(const void* g, const void* x, void* dx, const float* coe
   p.coef_c = const_cast<float*>(coef) + 2 * C;
   const dim3 grid(apply_grid(nvec)), blk(kThreads);
   return with_au([&](auto au) {
-    hipLaunchKernelGGL((bn_bwd_apply_g_kernel<T, decltype(au)::value>), grid, blk, (size_t)3 * C * sizeof(float), s,
-                       static_cast<const T*>(g), static_cast<const T*>(x), static_cast<T*>(dx), p, nvec, C, dir(8));
+    return launch_lds(bn_bwd_apply_g_kernel<T, decltype(au)::value>, grid, blk, (size_t)3 * C * sizeof(float), s,
+                      static_cast<const T*>(g), static_cast<const T*>(x), static_cast<T*>(dx), p, nvec, C, dir(8));
   });
 }
 
@@ -1004,6 +1046,13 @@ int64_t bn_workspace_floats(int64_t M, int C, int dtype) {
   const Geom g = dtype == kF32 ? geom<float>(M, C) : geom<uint16_t>(M, C);
   return (int64_t)2 * g.gx * C;
 }
+// the reduction grid of an [M, C] tensor as the launches take it: out = TC, RPI, gx, gy (tests)
+void bn_geometry(int64_t M, int C, int dtype, int out[4]) {
+  const Geom g = dtype == kF32 ? geom<float>(M, C) : geom<uint16_t>(M, C);
+  out[0] = g.TC, out[1] = g.RPI, out[2] = g.gx, out[3] = g.gy;
+}
+// widest C of the native path: bn_bwd_apply_kernel<MASK 2> stages 5 floats per channel in LDS
+int bn_max_channels() { return (int)(kLdsMax / (5 * sizeof(float))); }
 int bn_num_tickets(int C, int dtype) {
   const int V = dtype == kF32 ? 4 : 8;
   const int cv = C / V, mt = min_tc();
@@ -1018,7 +1067,7 @@ int fence_handoff() {
 }
 
 hipError_t bn_forward_train(const BnFwdArgs& a0, hipStream_t s) {
-  if (a0.M <= 0 || a0.C <= 0) return hipErrorInvalidValue;
+  if (a0.M <= 0 || a0.C <= 0 || a0.C > bn_max_channels()) return hipErrorInvalidValue;
   BnFwdArgs a = a0;
   a.p.fence_handoff = fence_handoff();
   return a.dtype == kF32 ? fwd_impl<float>(a, s) : fwd_impl<uint16_t>(a, s);
@@ -1026,13 +1075,13 @@ hipError_t bn_forward_train(const BnFwdArgs& a0, hipStream_t s) {
 
 hipError_t bn_apply(const void* x, const void* residual, void* y, int dtype, const float* scale, const float* shift,
                     int64_t M, int C, int relu, hipStream_t s) {
-  if (M <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (M <= 0 || C <= 0 || C > bn_max_channels()) return hipErrorInvalidValue;
   return dtype == kF32 ? apply_impl<float>(x, residual, y, scale, shift, M, C, relu, s)
                        : apply_impl<uint16_t>(x, residual, y, scale, shift, M, C, relu, s);
 }
 
 hipError_t bn_backward(const BnBwdArgs& a0, hipStream_t s) {
-  if (a0.M <= 0 || a0.C <= 0) return hipErrorInvalidValue;
+  if (a0.M <= 0 || a0.C <= 0 || a0.C > bn_max_channels()) return hipErrorInvalidValue;
   BnBwdArgs a = a0;
   a.p.fence_handoff = fence_handoff();
   return a.dtype == kF32 ? bwd_impl<float>(a, s) : bwd_impl<uint16_t>(a, s);
@@ -1040,7 +1089,7 @@ hipError_t bn_backward(const BnBwdArgs& a0, hipStream_t s) {
 
 hipError_t bn_sync_stats(const void* x, int dtype, int64_t M, int C, float* workspace, int* tickets, double* rec,
                          hipStream_t s) {
-  if (M <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (M <= 0 || C <= 0 || C > bn_max_channels()) return hipErrorInvalidValue;
   return dtype == kF32 ? sync_stats_impl<float>(x, M, C, workspace, tickets, rec, fence_handoff(), s)
                        : sync_stats_impl<uint16_t>(x, M, C, workspace, tickets, rec, fence_handoff(), s);
 }
@@ -1053,7 +1102,7 @@ hipError_t bn_sync_merge(const double* rec, int W, int C, const BnParams& p, dou
 }
 
 hipError_t bn_sync_backward_reduce(const BnBwdArgs& a0, double* sums, hipStream_t s) {
-  if (a0.M <= 0 || a0.C <= 0) return hipErrorInvalidValue;
+  if (a0.M <= 0 || a0.C <= 0 || a0.C > bn_max_channels()) return hipErrorInvalidValue;
   BnBwdArgs a = a0;
   a.p.fence_handoff = fence_handoff();
   return a.dtype == kF32 ? sync_reduce_impl<float>(a, sums, s) : sync_reduce_impl<uint16_t>(a, sums, s);
@@ -1068,7 +1117,7 @@ hipError_t bn_sync_coef(const double* sums, const double* count, int C, const Bn
 
 hipError_t bn_backward_apply_g(const void* g, const void* x, void* dx, int dtype, const float* coef, int64_t M, int C,
                                hipStream_t s) {
-  if (M <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (M <= 0 || C <= 0 || C > bn_max_channels()) return hipErrorInvalidValue;
   return dtype == kF32 ? apply_g_impl<float>(g, x, dx, coef, M, C, s) : apply_g_impl<uint16_t>(g, x, dx, coef, M, C, s);
 }
 

@@ -567,6 +567,8 @@ struct BnBwdArgs {
 };
 int64_t bn_workspace_floats(int64_t M, int C, int dtype);
 int bn_num_tickets(int C, int dtype);
+void bn_geometry(int64_t M, int C, int dtype, int out[4]);  // TC, RPI, gx (row blocks), gy (channel tiles)
+int bn_max_channels();  // widest C these kernels take (per-channel tables in LDS); wider: hipErrorInvalidValue
 hipError_t bn_forward_train(const BnFwdArgs& a, hipStream_t s);
 hipError_t bn_backward(const BnBwdArgs& a, hipStream_t s);
 // Cross-rank statistics (SyncBatchNorm): each reduction stops before the local row count

@@ -10,7 +10,8 @@
 // window with 16-B loads and writes y plus an argmax byte per element
 // (window offset dy*kw + dx); the backward visits the <= ceil(k/s)^2 output
 // windows covering its pixel and adds the dy entries whose argmax points at it.
-// NaN propagates like torch (a NaN wins the max).
+// NaN propagates like torch (a NaN wins the max); ties and all -inf windows go to the
+// first in-range tap in row-major window order, as in torch.
 #include "common.h"
 #include "kernels.h"
 
@@ -85,6 +86,9 @@ __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(const T* __restri
       }
     }
     const int h0 = ho * a.sh - a.ph, w0 = wo * a.sw - a.pw;
+    // the first in-range tap always takes the argmax, so a window whose taps are all -inf points
+    // at a real pixel (torch's rule), not at offset 0, which may lie in the padding
+    bool seen = false;
     for (int dy = 0; dy < a.kh; ++dy) {
       const int h = h0 + dy;
       if (h < 0 || h >= a.H) continue;
@@ -104,12 +108,13 @@ __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(const T* __restri
         const uint32_t k = (uint32_t)(dy * a.kw + dx);
 #pragma unroll
         for (int v = 0; v < V; ++v)
-          if (v_[v] > best[v] || v_[v] != v_[v]) {  // NaN wins (and stays: NaN > x is false)
+          if (v_[v] > best[v] || v_[v] != v_[v] || !seen) {  // NaN wins (and stays: NaN > x is false)
             if (best[v] == best[v]) {
               best[v] = v_[v];
               bi[v] = k;
             }
           }
+        seen = true;
       }
     }
     const int64_t o = (((int64_t)n * a.Ho + ho) * a.Wo + wo) * a.C + c0;

@@ -14,7 +14,7 @@ With a residual, the forward also writes the ReLU mask as bits (1/16 of the
 activation in bf16) and the backward's reduce pass writes the masked gradient
 (the residual gradient itself), so its apply pass reads that and x only.
 Eval mode applies the running statistics in one launch. Anything else (NCHW,
-CPU, momentum=None, odd channel counts) uses PyTorch's batch_norm with the same
+CPU, momentum=None, odd channel counts, more than 8192 channels) uses PyTorch's batch_norm with the same
 semantics. Parameters, buffers and state_dict keys are nn.BatchNorm2d's.
 
 ``SyncBatchNorm`` is the same layer with training statistics over every rank of a
@@ -35,6 +35,8 @@ def _rows_layout_ok(x: torch.Tensor) -> bool:
         return False
     vec = 4 if x.dtype == torch.float32 else 8
     if x.dim() < 2 or x.shape[1] % vec or x.data_ptr() % 16 or x.numel() == 0:
+        return False
+    if x.shape[1] > native().bn_max_channels():  # the elementwise passes keep per-channel tables in LDS
         return False
     if x.dim() == 2:
         return x.is_contiguous()

@@ -76,6 +76,7 @@ def test_native_bn_train_fwd_bwd(shape, dtype, relu, res):
     ours = BatchNorm2d(C).to(dev)
     with torch.no_grad():
         ours.weight.uniform_(0.5, 1.5)
+        ours.weight.mul_(torch.where(torch.rand(C, device=dev) < 0.5, -1.0, 1.0))  # both signs
         ours.bias.uniform_(-0.5, 0.5)
         ours.running_mean.uniform_(-1, 1)
     ref = nn.BatchNorm2d(C).to(dev)
