@@ -32,6 +32,13 @@ def _choices():
     return tuning.choices()
 
 
+def _trust_summary(name, opt):
+    """The trust ratios of the last step (read after the timed loop): min / median / max over the adapted tensors."""
+    ratios = sorted(r for r, _, _ in opt.trust_ratios().values())
+    return {"optimizer": name, "trust_ratio": {"min": ratios[0], "median": ratios[len(ratios) // 2], "max": ratios[-1],
+                                               "tensors": len(ratios)}}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch_size", type=int, default=128, help="per-GPU batch")
@@ -74,7 +81,13 @@ def main(argv=None):
                          "ops.lr_scheduler (native; the rate lives on the device and the schedule is captured with "
                          "the step) or torch.optim.lr_scheduler (--impl torch). Default: none")
     ap.add_argument("--lr_warmup_steps", type=int, default=5, help="warm-up length of --lr_schedule")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb"],
+                    help="sgd: FusedSGD / torch.optim.SGD. lars / lamb (native only): FusedLARS / FusedLAMB over "
+                         "layerwise_param_groups (weights adapted and decayed; BN and biases neither); the JSON line "
+                         "then carries the trust ratios of the last step")
     a = ap.parse_args(argv)
+    if a.optimizer != "sgd" and a.impl == "torch":
+        ap.error(f"--optimizer {a.optimizer} has no stock torch comparator: use --impl native")
     torch.backends.cudnn.benchmark = not a.no_cudnn_benchmark and not a.deterministic
     torch.backends.cudnn.deterministic = a.deterministic
 
@@ -103,8 +116,18 @@ def main(argv=None):
             model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
     if a.impl == "native":
         ddp = DistributedDataParallel(model, device_ids=[dev.index], comm=comm, bucket_cap_mb=a.bucket_cap_mb)
-        opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4,
-                       bf16_shadow=a.dtype == "bf16" and not a.no_shadow)
+        if a.optimizer == "sgd":
+            opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4,
+                           bf16_shadow=a.dtype == "bf16" and not a.no_shadow)
+        elif a.optimizer == "lars":
+            from pytorch_distributed_training_tutorials_amd.ops.optim import FusedLARS, layerwise_param_groups
+
+            opt = FusedLARS(layerwise_param_groups(model, 1e-4), lr=0.1, momentum=0.9,
+                            bf16_shadow=a.dtype == "bf16" and not a.no_shadow)
+        else:
+            from pytorch_distributed_training_tutorials_amd.ops.optim import FusedLAMB, layerwise_param_groups
+
+            opt = FusedLAMB(layerwise_param_groups(model, 1e-4, adapt=False), lr=1e-3)
     else:
         from torch.nn.parallel import DistributedDataParallel as TorchDDP
 
@@ -271,6 +294,7 @@ def main(argv=None):
             **({"lr_schedule": a.lr_schedule, "lr_warmup_steps": a.lr_warmup_steps,
                 "lr_schedule_steps": int(sched.last_epoch), "last_lr": [float(v) for v in sched.get_last_lr()]}
                if sched is not None else {}),
+            **(_trust_summary(a.optimizer, opt) if a.optimizer != "sgd" else {}),
             "final_loss": final, "finite": True, "kernel_choices": _choices(), "steps_total": executed + a.steps, **({"tag": a.tag} if a.tag else {}),
         }), flush=True)
     env.destroy_process_group()

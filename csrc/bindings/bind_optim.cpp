@@ -73,6 +73,41 @@ TensorList tensor_list(const std::vector<Tensor>& ps, const std::vector<Tensor>&
   return l;
 }
 
+// The slot filler of an SGD-shaped TensorList (sgd_multi_, lars_multi_): layout and dtype checks of
+// pair i, s1 = momentum buffer or null, s2 = bf16 shadow or null.
+auto sgd_slots(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs, const std::vector<Tensor>& moms,
+               const std::vector<Tensor>& shadows, int dt, const char* who) {
+  return [&ps, &gs, &moms, &shadows, dt, who](TensorList& l, size_t k, size_t i) {
+    check_dense_like(ps[i], ps[i], "param");
+    check_dense_like(ps[i], gs[i], "grad");
+    if (!moms.empty()) check_dense_like(ps[i], moms[i], "momentum buffer");
+    TORCH_CHECK(dt_of(ps[i]) == dt && gs[i].scalar_type() == ps[i].scalar_type() && gs[i].numel() == ps[i].numel());
+    l.s1[k] = moms.empty() ? nullptr : moms[i].data_ptr<float>();
+    l.s2[k] = nullptr;
+    if (!shadows.empty()) {
+      TORCH_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].numel() == ps[i].numel(), who,
+                  ": shadow must be a bf16 tensor of the param's size");
+      check_dense_like(ps[i], shadows[i], "bf16 shadow");
+      l.s2[k] = reinterpret_cast<float*>(shadows[i].data_ptr());
+    }
+  };
+}
+
+// The slot filler of an Adam-shaped TensorList (adam_multi_, lamb_multi_): s1 = exp_avg, s2 = exp_avg_sq.
+auto adam_slots(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs, const std::vector<Tensor>& ms,
+                const std::vector<Tensor>& vs, int dt) {
+  return [&ps, &gs, &ms, &vs, dt](TensorList& l, size_t k, size_t i) {
+    check_dense_like(ps[i], ps[i], "param");
+    check_dense_like(ps[i], gs[i], "grad");
+    check_dense_like(ps[i], ms[i], "exp_avg");
+    check_dense_like(ps[i], vs[i], "exp_avg_sq");
+    TORCH_CHECK(dt_of(ps[i]) == dt && gs[i].numel() == ps[i].numel());
+    TORCH_CHECK(ms[i].scalar_type() == at::kFloat && vs[i].scalar_type() == at::kFloat);
+    l.s1[k] = ms[i].data_ptr<float>();
+    l.s2[k] = vs[i].data_ptr<float>();
+  };
+}
+
 void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> moms,
                 c10::optional<Tensor> step, double lr, double momentum, double dampening, double wd,
                 bool nesterov, double grad_scale, std::vector<Tensor> shadows, c10::optional<Tensor> gcoef,
@@ -84,20 +119,7 @@ void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tens
   const int dt = dt_of(ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
   for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
-    const TensorList tl = tensor_list(ps, gs, a, b, [&](TensorList& l, size_t k, size_t i) {
-      check_dense_like(ps[i], ps[i], "param");
-      check_dense_like(ps[i], gs[i], "grad");
-      if (!moms.empty()) check_dense_like(ps[i], moms[i], "momentum buffer");
-      TORCH_CHECK(dt_of(ps[i]) == dt && gs[i].scalar_type() == ps[i].scalar_type() && gs[i].numel() == ps[i].numel());
-      l.s1[k] = moms.empty() ? nullptr : moms[i].data_ptr<float>();
-      l.s2[k] = nullptr;
-      if (!shadows.empty()) {
-        TORCH_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].numel() == ps[i].numel(),
-                    "sgd_multi_: shadow must be a bf16 tensor of the param's size");
-        check_dense_like(ps[i], shadows[i], "bf16 shadow");
-        l.s2[k] = reinterpret_cast<float*>(shadows[i].data_ptr());
-      }
-    });
+    const TensorList tl = tensor_list(ps, gs, a, b, sgd_slots(ps, gs, moms, shadows, dt, "sgd_multi_"));
     hip_check(sgd_multi(tl, dt, ptr_or_null<int32_t>(step), (float)lr, (float)momentum, (float)dampening,
                         (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
                         lr_dev_ptr(lr_dev, ps[0])),
@@ -114,20 +136,95 @@ void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
   const int dt = dt_of(ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
   for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
-    const TensorList tl = tensor_list(ps, gs, a, b, [&](TensorList& l, size_t k, size_t i) {
-      check_dense_like(ps[i], ps[i], "param");
-      check_dense_like(ps[i], gs[i], "grad");
-      check_dense_like(ps[i], ms[i], "exp_avg");
-      check_dense_like(ps[i], vs[i], "exp_avg_sq");
-      TORCH_CHECK(dt_of(ps[i]) == dt && gs[i].numel() == ps[i].numel());
-      TORCH_CHECK(ms[i].scalar_type() == at::kFloat && vs[i].scalar_type() == at::kFloat);
-      l.s1[k] = ms[i].data_ptr<float>();
-      l.s2[k] = vs[i].data_ptr<float>();
-    });
+    const TensorList tl = tensor_list(ps, gs, a, b, adam_slots(ps, gs, ms, vs, dt));
     hip_check(adam_multi(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)b1, (float)b2, (float)eps,
                          (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
                         lr_dev_ptr(lr_dev, ps[0])),
               "adam_multi");
+  });
+}
+
+// ------------------------------------------------------------- layer-wise adaptive rates
+// The workspace, the ratio record and the step counter of a layer-wise step, checked against the
+// parameter list: ws float32 with two slots per chunk of every tensor, rec float32[3][tensors]
+// (ratio, w, n), step int32[1]; all on the parameters' device.
+void check_layerwise(const std::vector<Tensor>& ps, const Tensor& step, const Tensor& ws, const Tensor& rec,
+                     const char* who) {
+  const Tensor& p = ps[0];
+  int64_t chunks = 0;
+  for (const Tensor& t : ps) {
+    TORCH_CHECK(t.is_cuda() && t.device() == p.device(), who, ": one device per call");
+    chunks += (t.numel() + kChunk - 1) / kChunk;
+  }
+  TORCH_CHECK(step.is_cuda() && step.device() == p.device() && step.scalar_type() == at::kInt && step.numel() == 1,
+              who, ": step must be int32[1] on the parameters' device");
+  TORCH_CHECK(ws.is_cuda() && ws.device() == p.device() && ws.scalar_type() == at::kFloat && ws.is_contiguous() &&
+                  ws.numel() >= 2 * chunks && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 8 == 0,
+              who, ": ws must be contiguous float32 on the parameters' device, two slots per chunk (", 2 * chunks, ")");
+  TORCH_CHECK(rec.is_cuda() && rec.device() == p.device() && rec.scalar_type() == at::kFloat && rec.is_contiguous() &&
+                  rec.numel() == 3 * (int64_t)ps.size(),
+              who, ": rec must be contiguous float32[3][", ps.size(), "] on the parameters' device");
+}
+
+// LARS over an SGD-shaped list: per <= 32 tensors, partials -> finalise -> update. The caller
+// advances the step counter afterwards, as after sgd_multi_.
+void lars_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> moms, Tensor step, double lr,
+                 double momentum, double dampening, double wd, bool nesterov, double grad_scale,
+                 double trust_coefficient, double eps, std::vector<Tensor> shadows, Tensor ws, Tensor rec,
+                 c10::optional<Tensor> gcoef, c10::optional<Tensor> lr_dev) {
+  if (ps.empty()) return;
+  TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
+  TORCH_CHECK(momentum == 0.0 || !moms.empty(), "lars_multi_: momentum needs momentum buffers");
+  TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat),
+              "lars_multi_: bf16 shadows need one per (f32) param");
+  check_layerwise(ps, step, ws, rec, "lars_multi_");
+  const int dt = dt_of(ps[0]);
+  const int64_t T = (int64_t)ps.size();
+  const TrustRule rule{kTrustLars, 1, (float)trust_coefficient, (float)wd, (float)eps, (float)grad_scale};
+  c10::hip::HIPGuard guard(ps[0].device().index());
+  hipStream_t s = cur_stream(ps[0]);
+  const float* gc = gcoef_ptr(gcoef, ps[0]);
+  int64_t slot = 0;
+  for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
+    const TensorList tl = tensor_list(ps, gs, a, b, sgd_slots(ps, gs, moms, shadows, dt, "lars_multi_"));
+    hip_check(lars_partials(tl, dt, ws.data_ptr<float>(), slot, s), "lars_partials");
+    hip_check(trust_finalize(tl, ws.data_ptr<float>(), slot, rule, gc, rec.data_ptr<float>(), (int64_t)a, T, s),
+              "trust_finalize");
+    hip_check(lars_update(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)momentum, (float)dampening, (float)wd,
+                          nesterov, (float)grad_scale, rec.data_ptr<float>() + a, s, gc, lr_dev_ptr(lr_dev, ps[0])),
+              "lars_update");
+    slot += chunk_blocks(tl);
+  });
+}
+
+// LAMB over an Adam-shaped list: per <= 32 tensors, moments + partials -> finalise -> update.
+// step already counts this update, as for adam_multi_.
+void lamb_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> ms, std::vector<Tensor> vs,
+                 Tensor step, double lr, double b1, double b2, double eps, double wd, bool bias_correction, bool adapt,
+                 double grad_scale, Tensor ws, Tensor rec, c10::optional<Tensor> gcoef, c10::optional<Tensor> lr_dev) {
+  if (ps.empty()) return;
+  TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
+  check_layerwise(ps, step, ws, rec, "lamb_multi_");
+  const int dt = dt_of(ps[0]);
+  const int64_t T = (int64_t)ps.size();
+  const TrustRule rule{kTrustLamb, adapt ? 1 : 0, 0.f, 0.f, 0.f, 1.f};
+  c10::hip::HIPGuard guard(ps[0].device().index());
+  hipStream_t s = cur_stream(ps[0]);
+  const int32_t* st = step.data_ptr<int32_t>();
+  int64_t slot = 0;
+  for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
+    const TensorList tl = tensor_list(ps, gs, a, b, adam_slots(ps, gs, ms, vs, dt));
+    for (size_t i = a; i < b; ++i)
+      TORCH_CHECK(gs[i].scalar_type() == ps[i].scalar_type(), "lamb_multi_: a gradient of its parameter's dtype");
+    hip_check(lamb_moments(tl, dt, st, (float)b1, (float)b2, (float)eps, (float)wd, bias_correction, (float)grad_scale,
+                           ws.data_ptr<float>(), slot, s, gcoef_ptr(gcoef, ps[0])),
+              "lamb_moments");
+    hip_check(trust_finalize(tl, ws.data_ptr<float>(), slot, rule, nullptr, rec.data_ptr<float>(), (int64_t)a, T, s),
+              "trust_finalize");
+    hip_check(lamb_update(tl, dt, st, (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, bias_correction,
+                          rec.data_ptr<float>() + a, s, lr_dev_ptr(lr_dev, ps[0])),
+              "lamb_update");
+    slot += chunk_blocks(tl);
   });
 }
 
@@ -301,6 +398,15 @@ void bind_optim(py::module_& m) {
   m.def("adam_multi_", &adam_multi_, py::arg("ps"), py::arg("gs"), py::arg("ms"), py::arg("vs"), py::arg("step"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("decoupled"),
         py::arg("grad_scale"), py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none());
+  m.def("lars_multi_", &lars_multi_, py::arg("ps"), py::arg("gs"), py::arg("moms"), py::arg("step"), py::arg("lr"),
+        py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"),
+        py::arg("trust_coefficient"), py::arg("eps"), py::arg("shadows"), py::arg("ws"), py::arg("rec"),
+        py::arg("gcoef") = py::none(), py::arg("lr_dev") = py::none(),
+        "LARS: rec = {ratio, |p|, |g'|} per tensor, then the SGD step on ratio * (g' + wd p)");
+  m.def("lamb_multi_", &lamb_multi_, py::arg("ps"), py::arg("gs"), py::arg("ms"), py::arg("vs"), py::arg("step"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bias_correction"),
+        py::arg("adapt"), py::arg("grad_scale"), py::arg("ws"), py::arg("rec"), py::arg("gcoef") = py::none(),
+        py::arg("lr_dev") = py::none(), "LAMB: moments, rec = {ratio, |p|, |u|} per tensor, p -= lr ratio u");
   m.def("clip_norm_partials_", &clip_norm_partials_, py::arg("spans"), py::arg("ws"), py::arg("first_slot"),
         py::arg("norm"), "per-chunk norm partials (norm 0: sum of squares, 1: max |g|); returns the slot count");
   m.def("clip_norm_finalize_", &clip_norm_finalize_, py::arg("ws"), py::arg("n"), py::arg("norm"), py::arg("max_norm"),

@@ -284,6 +284,47 @@ hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, f
 hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
                       hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
+// --------------------------------------------------------------------------
+// Layer-wise adaptive rates (csrc/kernels/layerwise.hip): LARS on the SGD update, LAMB on Adam's
+// moments. Three launches per TensorList, all capturable and deterministic (no atomics, no memsets,
+// no host reads): partials -> finalise -> update. With g' = grad_scale * gcoef * g:
+//   LARS: w = |p|, n = |g'|, ratio = coef w / (n + wd w + eps) if w > 0 and n > 0 else 1,
+//         d = ratio (g' + wd p), then the momentum-SGD step of sgd_multi on d.
+//   LAMB: m, v as Adam on g'; u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd p; w = |p|, n = |u|,
+//         ratio = w / n if adapt and w > 0 and n > 0 else 1; p -= lr ratio u.
+// ws: two f32 slots per kChunk-element chunk, chunk b of a launch at ws[2 (first_slot + b)]; every
+// slot has one writer. rec: f32 [3][tensors] = ratio, w, n; tensor t of a launch at column
+// first_tensor + t. Norms are taken over the stored values widened to f32.
+enum TrustKind : int { kTrustLars = 0, kTrustLamb = 1 };
+struct TrustRule {
+  int kind;                   // TrustKind
+  int adapt;                  // kTrustLamb: 0 leaves ratio = 1 (w and n are still recorded)
+  float coef, wd, eps;        // kTrustLars: trust coefficient, weight decay, eps
+  float gscale;               // kTrustLars: grad_scale; |gscale * gcoef| scales the raw-gradient norm
+};
+struct NumelList {
+  int n;
+  int64_t numel[kMaxTensorsPerLaunch];
+};
+// sum p^2 and sum g^2 (raw g) per chunk
+hipError_t lars_partials(const TensorList& tl, int dtype, float* ws, int64_t first_slot, hipStream_t s);
+// one wave per tensor of tl: fixed-order float64 sums of its slots, then the rule
+hipError_t trust_finalize(const TensorList& tl, const float* ws, int64_t first_slot, const TrustRule& r,
+                          const float* gcoef, float* rec, int64_t first_tensor, int64_t tensors, hipStream_t s);
+// sgd_multi with d = ratio[t] (g' + wd p); tl as sgd_multi (s1 momentum, s2 optional bf16 shadow)
+hipError_t lars_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float momentum,
+                       float dampening, float weight_decay, int nesterov, float grad_scale, const float* ratio,
+                       hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
+// tl as adam_multi (s1 exp_avg, s2 exp_avg_sq); step already counts this update. Updates and stores
+// m and v, writes sum p^2 and sum u^2 per chunk.
+hipError_t lamb_moments(const TensorList& tl, int dtype, const int32_t* step, float beta1, float beta2, float eps,
+                        float weight_decay, int bias_correction, float grad_scale, float* ws, int64_t first_slot,
+                        hipStream_t s, const float* gcoef = nullptr);
+// p -= lr ratio[t] u, u recomputed from the stored m, v and p by the function lamb_moments used
+hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int bias_correction, const float* ratio, hipStream_t s,
+                       const float* lr_dev = nullptr);
+
 // dst[i] = src_i * scale over a list (bucket pack) or the reverse (unpack).
 struct CopyList {
   int n;

@@ -7,4 +7,4 @@ from .loss import CrossEntropyLoss, MSELoss, cross_entropy, mse_loss  # noqa: F4
 from .lr_scheduler import (ConstantLR, CosineAnnealingLR, ExponentialLR, LinearLR, MultiStepLR,  # noqa: F401
                            PolynomialLR, SequentialLR, StepLR)
 from .norm import BatchNorm2d, SyncBatchNorm  # noqa: F401
-from .optim import FusedAdam, FusedSGD  # noqa: F401
+from .optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD, layerwise_param_groups  # noqa: F401

@@ -20,7 +20,10 @@ names, per-parameter state keys ``momentum_buffer`` / ``exp_avg`` /
     they load it, so the clipped gradients are never written;
   * a learning-rate schedule (:mod:`.lr_scheduler`) can be bound: a device float per
     (group, device) that the kernels load in place of ``group["lr"]``, so the learning rate
-    moves inside a captured step.
+    moves inside a captured step;
+  * :class:`FusedLARS` / :class:`FusedLAMB` put a layer-wise trust ratio on top of the two
+    (csrc/kernels/layerwise.hip): norms, ratio and update stay on the device, so the step
+    remains capturable; :func:`layerwise_param_groups` builds their usual two groups.
 """
 from __future__ import annotations
 
@@ -360,3 +363,233 @@ class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
             v.mul_(b2).addcmul_(g, g, value=1 - b2)
             denom = v.sqrt() / bc2s + eps
             p.addcdiv_(m, denom, value=-lr / bc1)
+
+
+# ---------------------------------------------------------------------------- layer-wise rates
+_CHUNK = 4096  # kChunk
+
+
+class _TrustPlan:
+    """Launch plan of one adapted cohort: the workspace (two float32 slots per 4096-element chunk)
+    and the record ``rec[3, T]`` = (ratio, ||p||, ||g'|| or ||u||) per tensor, valid while the
+    parameters and gradients stay where ``key`` saw them."""
+
+    def __init__(self, ps, key):
+        self.params = list(ps)
+        self.key = key
+        device = ps[0].device
+        chunks = sum(-(-p.numel() // _CHUNK) for p in ps)
+        self.ws = torch.empty(2 * max(chunks, 1), dtype=torch.float32, device=device)
+        self.rec = torch.ones(3, len(ps), dtype=torch.float32, device=device)
+
+
+class _TrustRatios:
+    """Launch plans and the trust-ratio record of the layer-wise optimizers. A plan per (group,
+    device, dtype, cohort) is cached and keyed on the tensors' (data_ptr, numel); it is built on the
+    first eager step -- :class:`utils.graphs.GraphedStep`'s warm-up creates it before capture -- and
+    rebuilt when a parameter or a gradient moves. After that ``step()`` allocates nothing."""
+
+    def _init_trust(self):
+        self._trust_plans: dict = {}  # (group index, id of the cohort's counter) -> (counter, _TrustPlan)
+        self._trust_cpu: dict = {}    # CPU parameters: parameter -> (ratio, w, n)
+
+    def _trust_plan(self, gi, step, ps, grads) -> _TrustPlan:
+        key = [(p.data_ptr(), g.data_ptr(), p.numel()) for p, g in zip(ps, grads)]
+        held = self._trust_plans.get((gi, id(step)))
+        if held is not None and held[1].key == key:
+            return held[1]
+        plan = _TrustPlan(ps, key)
+        mine = set(ps)  # a parameter reports through one plan: drop the plans it has left
+        self._trust_plans = {k: v for k, v in self._trust_plans.items() if mine.isdisjoint(v[1].params)}
+        self._trust_plans[(gi, id(step))] = (step, plan)  # holding the counter keeps its id unique
+        return plan
+
+    def trust_ratios(self) -> dict:
+        """``{parameter: (ratio, w, n)}`` as the latest update of each parameter computed them:
+        ``w = ||p||`` before that update, ``n = ||g'||`` (LARS) or ``||u||`` (LAMB). Parameters of
+        unadapted LARS groups (``trust_coefficient=0``) take plain SGD and are not listed. Reads the
+        device records back, so call it outside the step (and outside a capture): for logging."""
+        out = {}
+        for _, plan in self._trust_plans.values():
+            rec = plan.rec.cpu()
+            for i, p in enumerate(plan.params):
+                out[p] = (float(rec[0, i]), float(rec[1, i]), float(rec[2, i]))
+        out.update(self._trust_cpu)
+        return out
+
+    def _restore_group_keys(self, before) -> None:
+        """After ``load_state_dict``: a checkpoint of the parent class has no layer-wise group keys;
+        those keep the values this optimizer was constructed with."""
+        for group, old in zip(self.param_groups, before):
+            for k, v in old.items():
+                group.setdefault(k, v)
+
+
+def _norm64(x: torch.Tensor) -> torch.Tensor:
+    return torch.linalg.vector_norm(x.double())
+
+
+class FusedLARS(_TrustRatios, FusedSGD):
+    """LARS (You et al. 2017, as apex LARC / lightning-bolts scale it) on :class:`FusedSGD`: with the
+    effective gradient ``g' = gscale * gcoef * g``, ``w = ||p||`` and ``n = ||g'||``, every tensor's
+    decayed gradient is scaled by ``ratio = trust_coefficient * w / (n + weight_decay * w + eps)``
+    (1 when ``w`` or ``n`` is not positive) before the momentum-SGD step. Three capturable launches
+    per 32 tensors: per-chunk partial sums, a fixed-order float64 finalise per tensor, the update
+    (csrc/kernels/layerwise.hip); the ratios stay on the device (:meth:`trust_ratios` reads them).
+
+    A group with ``trust_coefficient=0`` is not adapted: it takes exactly :class:`FusedSGD`'s launches.
+    Adapted groups always take the multi-tensor form, even when their parameters form one flat span:
+    the flat kernels have no tensor index. State and ``state_dict`` layout are ``FusedSGD``'s, so
+    checkpoints interchange; fused clipping, the schedulers and ``bf16_shadow`` work as there."""
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, maximize: bool = False,
+                 bf16_shadow: bool = False, trust_coefficient: float = 1e-3, eps: float = 1e-8):
+        if trust_coefficient < 0.0:
+            raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid eps: {eps}")
+        super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize, bf16_shadow)
+        self.defaults.update(trust_coefficient=trust_coefficient, eps=eps)
+        for group in self.param_groups:
+            group.setdefault("trust_coefficient", trust_coefficient)
+            group.setdefault("eps", eps)
+            if group["trust_coefficient"] < 0.0 or group["eps"] < 0.0:
+                raise ValueError("trust_coefficient and eps must not be negative")
+        self._init_trust()
+
+    def load_state_dict(self, state_dict):
+        before = [{k: g[k] for k in ("trust_coefficient", "eps")} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        self._restore_group_keys(before)
+
+    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None, lr_dev=None):
+        group = self.param_groups[gi]
+        if group["trust_coefficient"] == 0:
+            return super()._gpu_step(gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
+        grads = [p.grad for p in ps]
+        moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
+        shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and dtype == torch.float32) else []
+        plan = self._trust_plan(gi, step, ps, grads)
+        native().lars_multi_([p.data for p in ps], grads, moms, step, lr, mu, damp, wd, nest, gscale,
+                             group["trust_coefficient"], group["eps"], shadows, plan.ws, plan.rec, gcoef, lr_dev)
+        step.add_(1)
+        for p in ps if shadows else ():
+            p._ptdt_bf16_version = p._version  # the shadow is current until p changes
+
+    def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale, gcoef=None):
+        # FusedSGD.step hands the CPU path no group: find the one these parameters belong to
+        group = next(g for g in self.param_groups if any(q is ps[0] for q in g["params"]))
+        tc, eps = group["trust_coefficient"], group["eps"]
+        if tc == 0:
+            return super()._cpu_step(ps, lr, mu, damp, wd, nest, gscale, gcoef)
+        for p in ps:
+            g = p.grad * gscale
+            if gcoef is not None:
+                g = g * gcoef
+            w, n = _norm64(p), _norm64(g)
+            ratio = tc * w / (n + wd * w + eps) if (w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
+            self._trust_cpu[p] = (float(ratio), float(w), float(n))
+            d = g.add(p, alpha=wd) if wd != 0 else g
+            d = d * ratio.to(d.dtype)
+            if mu != 0:
+                buf = self.state[p].get("momentum_buffer")
+                if buf is None:
+                    buf = d.clone()
+                    self.state[p]["momentum_buffer"] = buf
+                else:
+                    buf.mul_(mu).add_(d, alpha=1 - damp)
+                d = d.add(buf, alpha=mu) if nest else buf
+            p.add_(d, alpha=-lr)
+
+
+class FusedLAMB(_TrustRatios, FusedAdam):
+    """LAMB (You et al. 2019; apex ``FusedLAMB`` without its built-in global clip, which
+    :class:`ops.clip.GradClipper` provides) on :class:`FusedAdam`'s state: Adam moments of the
+    effective gradient, ``u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay * p``,
+    ``ratio = ||p|| / ||u||`` (1 when a norm is not positive, or ``adapt=False``) and
+    ``p -= lr * ratio * u``. Three capturable launches per 32 tensors (csrc/kernels/layerwise.hip):
+    the moment update with per-chunk partial sums, a fixed-order float64 finalise per tensor, the
+    update, which recomputes ``u`` from the stored moments.
+
+    Every GPU group takes the multi-tensor form, even when its parameters form one flat span: the
+    flat kernels have no tensor index. State keys, ``state_dict`` layout and the per-parameter
+    ``step`` are ``FusedAdam``'s."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.0, bias_correction: bool = True, adapt: bool = True,
+                 maximize: bool = False):
+        if eps < 0.0:
+            raise ValueError(f"Invalid eps: {eps}")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize)
+        self.defaults.update(bias_correction=bias_correction, adapt=adapt)
+        for group in self.param_groups:
+            group.setdefault("bias_correction", bias_correction)
+            group.setdefault("adapt", adapt)
+            if group["eps"] < 0.0:
+                raise ValueError(f"Invalid eps: {group['eps']}")
+        self._init_trust()
+
+    def load_state_dict(self, state_dict):
+        before = [{k: g[k] for k in ("bias_correction", "adapt")} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        self._restore_group_keys(before)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        coefs = self._take_grad_coef()
+        for gi, group in enumerate(self.param_groups):
+            b1, b2 = group["betas"]
+            gscale = -1.0 if group["maximize"] else 1.0
+            for (device, dtype), sub in _split_by_device(group["params"]).items():
+                gcoef = coefs.get(device)
+                lr_dev = self._lr_dev(gi, device)
+                for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
+                    step.add_(1)
+                    ms, vs = self._state_lists(ps)
+                    if device.type != "cuda":
+                        self._cpu_step(ps, ms, vs, step, group, gscale, gcoef)
+                        continue
+                    grads = [p.grad for p in ps]
+                    plan = self._trust_plan(gi, step, ps, grads)
+                    native().lamb_multi_([p.data for p in ps], grads, ms, vs, step, group["lr"], b1, b2,
+                                         group["eps"], group["weight_decay"], group["bias_correction"],
+                                         group["adapt"], gscale, plan.ws, plan.rec, gcoef, lr_dev)
+        return loss
+
+    def _cpu_step(self, ps, ms, vs, step, group, gscale, gcoef=None):
+        t = float(step.item())
+        b1, b2 = group["betas"]
+        lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
+        bc1 = 1 - b1 ** t if group["bias_correction"] else 1.0
+        bc2s = (1 - b2 ** t) ** 0.5 if group["bias_correction"] else 1.0
+        for p, m, v in zip(ps, ms, vs):
+            g = p.grad.float() * gscale
+            if gcoef is not None:
+                g = g * gcoef
+            m.mul_(b1).add_(g, alpha=1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
+            u = (m / bc1) / (v.sqrt() / bc2s + eps)
+            if wd != 0:
+                u = u.add(p, alpha=wd)
+            w, n = _norm64(p), _norm64(u)
+            ratio = w / n if (group["adapt"] and w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
+            self._trust_cpu[p] = (float(ratio), float(w), float(n))
+            p.add_(u.to(p.dtype), alpha=-lr * float(ratio))
+
+
+def layerwise_param_groups(module: torch.nn.Module, weight_decay: float = 0.0, **adapt_off) -> list:
+    """The standard two parameter groups of a layer-wise optimizer: parameters with ``ndim > 1``
+    (conv and linear weights) are adapted and decayed with ``weight_decay``; BatchNorm weights and
+    all biases (``ndim <= 1``) get ``weight_decay=0`` and the options in ``adapt_off``, which switch
+    the adaptation off: ``trust_coefficient=0`` for :class:`FusedLARS` (the default when nothing is
+    given), ``adapt=False`` for :class:`FusedLAMB`. Parameters that need no gradient are left out."""
+    if not adapt_off:
+        adapt_off = {"trust_coefficient": 0.0}
+    params = [p for p in module.parameters() if p.requires_grad]
+    return [{"params": [p for p in params if p.ndim > 1], "weight_decay": weight_decay},
+            {"params": [p for p in params if p.ndim <= 1], "weight_decay": 0.0, **adapt_off}]

@@ -175,6 +175,10 @@ class Trainer:
                 raise ValueError(f"{engine} engine has a fixed learning rate: lr_scheduler needs engine='autograd'")
             if engine == "auto":
                 return "autograd"
+        if type(self.optimizer).__name__ in ("FusedLARS", "FusedLAMB"):  # no trust ratios in those engines
+            if engine in ("fused", "persistent"):
+                raise ValueError(f"{engine} engine has no layer-wise trust ratios: "
+                                 f"{type(self.optimizer).__name__} needs engine='autograd'")
         if engine == "auto":
             return "persistent" if self._fusable(model) else "autograd"
         if engine in ("fused", "persistent") and not self._fusable(model):
