@@ -85,6 +85,11 @@ def main(argv=None):
                     help="sgd: FusedSGD / torch.optim.SGD. lars / lamb (native only): FusedLARS / FusedLAMB over "
                          "layerwise_param_groups (weights adapted and decayed; BN and biases neither); the JSON line "
                          "then carries the trust ratios of the last step")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the weights with this decay, updated after every "
+                         "optimizer step: ops.AveragedModel (native; no host read, captured with the step, bf16 "
+                         "shadows like the optimizer's) or torch.optim.swa_utils.AveragedModel (--impl torch). "
+                         "Default: off")
     a = ap.parse_args(argv)
     if a.optimizer != "sgd" and a.impl == "torch":
         ap.error(f"--optimizer {a.optimizer} has no stock torch comparator: use --impl native")
@@ -151,6 +156,16 @@ def main(argv=None):
                  else S.StepLR(opt, step_size=max(1, span // 3), gamma=0.1))
         sched = S.SequentialLR(opt, [S.LinearLR(opt, start_factor=0.1, end_factor=1.0, total_iters=a.lr_warmup_steps),
                                      after], [a.lr_warmup_steps])
+    ema = None
+    if a.ema is not None:  # created once, before any capture: its averages and device counter are static
+        if a.impl == "native":
+            from pytorch_distributed_training_tutorials_amd.ops import AveragedModel
+
+            ema = AveragedModel(model, decay=a.ema, bf16_shadow=a.dtype == "bf16" and not a.no_shadow)
+        else:
+            from torch.optim.swa_utils import AveragedModel, get_ema_multi_avg_fn
+
+            ema = AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(a.ema))
     x = torch.empty(a.batch_size, 3, a.image, a.image, device=dev)
     native().philox_(x, 1234 + rank, 0, 1)
     if not a.no_channels_last:
@@ -188,6 +203,8 @@ def main(argv=None):
         opt.step()
         if sched is not None:
             sched.step()  # native: one single-wave launch, no host read -- part of the captured step
+        if ema is not None:
+            ema.update_parameters(model)  # native: no host read either -- part of the captured step
         if a.loss_curve and not torch.cuda.is_current_stream_capturing():
             curve.append(loss.detach().clone())
         return loss
@@ -295,6 +312,9 @@ def main(argv=None):
                 "lr_schedule_steps": int(sched.last_epoch), "last_lr": [float(v) for v in sched.get_last_lr()]}
                if sched is not None else {}),
             **(_trust_summary(a.optimizer, opt) if a.optimizer != "sgd" else {}),
+            **({"ema_decay": a.ema, "ema_updates": int(ema.n_averaged),
+                "ema_last_weight": ema.last_weight() if a.impl == "native" else 1.0 - a.ema}
+               if ema is not None else {}),
             "final_loss": final, "finite": True, "kernel_choices": _choices(), "steps_total": executed + a.steps, **({"tag": a.tag} if a.tag else {}),
         }), flush=True)
     env.destroy_process_group()

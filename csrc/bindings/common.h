@@ -27,6 +27,7 @@ using at::Tensor;
 // writes at def time (a class-typed argument is spelled by its Python name only once registered).
 void bind_engine(py::module_& m);
 void bind_optim(py::module_& m);
+void bind_averaging(py::module_& m);
 void bind_math(py::module_& m);
 void bind_norm(py::module_& m);
 void bind_int8(py::module_& m);

@@ -9,6 +9,7 @@ PYBIND11_MODULE(_C, m) {
   // been defined before that class is registered (their signatures spell it by its C++ name)
   bind_engine(m);
   bind_optim(m);
+  bind_averaging(m);
   bind_math(m);
   bind_norm(m);
   bind_int8(m);

@@ -325,6 +325,29 @@ hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, flo
                        float eps, float weight_decay, int bias_correction, const float* ratio, hipStream_t s,
                        const float* lr_dev = nullptr);
 
+// --------------------------------------------------------------------------
+// Weight averaging (csrc/kernels/averaging.hip): EMA / SWA of an fp32 average. All launches are
+// capturable (no atomics, no memsets, no host reads, no allocation).
+enum AvgKind : int { kAvgSwa = 0, kAvgEma = 1 };
+// Reads n (device int64, updates applied so far), writes the weight of this update to w (device
+// float32) and stores n + 1. In double, rounded once: n == 0: 1; SWA: 1 / (n + 1); EMA: 1 - decay,
+// with warmup 1 - min(decay, (1 + n) / (10 + n)). One wave, one thread working.
+hipError_t avg_prepare(int64_t* n, float* w, int kind, double decay, int warmup, hipStream_t s);
+struct AvgList {
+  int n;                                   // pairs in this launch
+  int64_t numel[kMaxTensorsPerLaunch];
+  float* a[kMaxTensorsPerLaunch];          // the fp32 average, updated in place
+  const void* p[kMaxTensorsPerLaunch];     // the source (f32 or bf16, see src_dtype), same memory order as a
+  uint16_t* shadow[kMaxTensorsPerLaunch];  // optional bf16 rounding of the new a (the autocast copy) or nullptr
+  uint16_t* copy[kMaxTensorsPerLaunch];    // bf16 sources: optional second bf16 rounding (the module's own
+                                           // parameter) or nullptr
+};
+// a = fmaf(*w, p - a, a) per element, a = p exactly when *w == 1.0f; one block per kChunk elements.
+hipError_t avg_update_multi(const AvgList& l, int src_dtype, const float* w, hipStream_t s);
+// the same over one pair of 1-D spans (and the spans of the optional bf16 copies)
+hipError_t avg_update_flat(float* a, const void* p, int src_dtype, uint16_t* shadow, uint16_t* copy, int64_t numel,
+                           const float* w, hipStream_t s);
+
 // dst[i] = src_i * scale over a list (bucket pack) or the reverse (unpack).
 struct CopyList {
   int n;

@@ -11,6 +11,7 @@
 // (full chunk, all pointers 16-byte aligned) or one by one (tail chunk, unaligned view), so the sums
 // and with them the ratios depend on the values alone, not on where a tensor lies. In the 16-byte
 // form every thread issues all its loads (8 for LARS, 16 for LAMB on f32) before it uses one.
+#include "chunk_elems.h"
 #include "chunks.h"
 #include "common.h"
 #include "kernels.h"
@@ -20,63 +21,14 @@
 namespace ptdt {
 namespace {
 
-constexpr int kBlock = kSgdBlock;
-constexpr int kElems = kChunk / kBlock;  // elements of a chunk per thread: 16
+constexpr int kBlock = kSgdBlock;  // kElems (chunk_elems.h) elements of a chunk per thread: 16
+static_assert(kBlock == kChunkThreads, "load_elems / store_elems walk a chunk with this block size");
 constexpr int kFinalBlock = 64;          // the finalise: one wave per tensor
 
 struct LambHyper {
   float lr, b1, b2, eps, wd, gscale;
   int bias_correction;
 };
-
-// Element e (< kElems) of this thread in a chunk whose threads own groups of V consecutive elements.
-template <int V>
-__device__ __forceinline__ int64_t elem_index(int64_t start, int e) {
-  return start + (int64_t)((e / V) * kBlock + (int)threadIdx.x) * V + (e % V);
-}
-
-// f[e] = x[elem_index<V>(start, e)]. FULL: the whole chunk exists and x is 16-byte aligned, 16-byte
-// loads. Otherwise element loads, elements at or past `end` read as 0.
-template <typename S, int V, bool FULL>
-__device__ __forceinline__ void load_elems(const S* x, int64_t start, int64_t end, float* f) {
-  constexpr int VS = Vec16<S>::N;
-  static_assert(V % VS == 0 && kElems % V == 0, "groups are whole 16-byte vectors");
-  if constexpr (FULL) {
-    u32x4 w[kElems / VS];
-#pragma unroll
-    for (int q = 0; q < kElems / VS; ++q) w[q] = *(const u32x4 PTDT_GLOBAL*)(x + elem_index<V>(start, q * VS));
-#pragma unroll
-    for (int q = 0; q < kElems / VS; ++q) Vec16<S>::unpack(w[q], f + q * VS);
-  } else {
-#pragma unroll
-    for (int e = 0; e < kElems; ++e) {
-      const int64_t i = elem_index<V>(start, e);
-      f[e] = i < end ? Cvt<S>::load(x, i) : 0.f;
-    }
-  }
-}
-
-template <typename S, int V, bool FULL>
-__device__ __forceinline__ void store_elems(S* x, int64_t start, int64_t end, const float* f) {
-  constexpr int VS = Vec16<S>::N;
-  if constexpr (FULL) {
-#pragma unroll
-    for (int q = 0; q < kElems / VS; ++q)
-      *(u32x4 PTDT_GLOBAL*)(x + elem_index<V>(start, q * VS)) = Vec16<S>::pack(f + q * VS);
-  } else {
-#pragma unroll
-    for (int e = 0; e < kElems; ++e) {
-      const int64_t i = elem_index<V>(start, e);
-      if (i < end) Cvt<S>::store(x, i, f[e]);
-    }
-  }
-}
-
-__device__ __forceinline__ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr,
-                                          const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
 
 // the two sums of a thread's elements: four accumulators each, joined in a fixed order
 struct Sum2 {

@@ -1,4 +1,5 @@
 """Native (gfx950 HIP) operators with autograd and CPU reference fallbacks."""
+from .averaging import AveragedModel  # noqa: F401
 from .clip import GradClipper, clip_grad_norm_, clip_grad_value_  # noqa: F401
 from .flat import FlatParameters, contiguous_span  # noqa: F401
 from .fused_step import FusedMLPStep  # noqa: F401

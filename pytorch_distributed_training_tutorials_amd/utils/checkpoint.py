@@ -7,7 +7,8 @@ every rank waits at a barrier, and resume restores the epoch so
 ``sampler.set_epoch`` continues the same permutation sequence. Files are
 written atomically (tmp + rename) and loaded with ``weights_only=True``.
 ``lr_scheduler=`` (ops/lr_scheduler.py) adds its state under ``"lr_scheduler"``;
-a checkpoint without that key loads as before.
+a checkpoint without that key loads as before. ``averaged_model=`` (ops/averaging.py)
+does the same under ``"averaged_model"``.
 """
 from __future__ import annotations
 
@@ -23,13 +24,15 @@ def _unwrap(sd: dict, prefix: str = "module.") -> dict:
 
 
 def save_checkpoint(path: str, model, optimizer=None, epoch: int = 0, rank: int = 0, extra: dict | None = None,
-                    barrier=None, lr_scheduler=None) -> None:
+                    barrier=None, lr_scheduler=None, averaged_model=None) -> None:
     if rank == 0:
         state = {"model": model.state_dict(), "epoch": int(epoch)}
         if optimizer is not None:
             state["optimizer"] = optimizer.state_dict()
         if lr_scheduler is not None:
             state["lr_scheduler"] = lr_scheduler.state_dict()
+        if averaged_model is not None:
+            state["averaged_model"] = averaged_model.state_dict()
         if extra:
             state.update(extra)
         d = os.path.dirname(os.path.abspath(path))
@@ -42,7 +45,7 @@ def save_checkpoint(path: str, model, optimizer=None, epoch: int = 0, rank: int 
 
 
 def load_checkpoint(path: str, model=None, optimizer=None, map_location="cpu", strict: bool = True,
-                    lr_scheduler=None) -> dict:
+                    lr_scheduler=None, averaged_model=None) -> dict:
     state = torch.load(path, map_location=map_location, weights_only=True)
     if model is not None:
         sd = state["model"]
@@ -55,4 +58,6 @@ def load_checkpoint(path: str, model=None, optimizer=None, map_location="cpu", s
         optimizer.load_state_dict(state["optimizer"])
     if lr_scheduler is not None and "lr_scheduler" in state:  # after the optimizer: it rewrites group["lr"]
         lr_scheduler.load_state_dict(state["lr_scheduler"])
+    if averaged_model is not None and "averaged_model" in state:
+        averaged_model.load_state_dict(state["averaged_model"], strict=strict)
     return state

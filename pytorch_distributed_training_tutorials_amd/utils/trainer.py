@@ -35,6 +35,10 @@ step (ops/clip.py; autograd engine only, which ``engine="auto"`` then selects).
 ``lr_scheduler=`` (ops/lr_scheduler.py: an instance bound to ``optimizer``, or a
 callable ``optimizer -> scheduler``) is stepped once per batch after
 ``optimizer.step()`` and saved in snapshots; autograd engine only, as clipping.
+``averaged_model=`` (ops/averaging.py: an ``AveragedModel``, or a callable
+``model -> AveragedModel`` called once the model is on its device) takes one
+``update_parameters`` per batch after the optimizer and the scheduler stepped, and is
+saved in snapshots; autograd engine only, as clipping.
 """
 from __future__ import annotations
 
@@ -89,11 +93,13 @@ def _sgd_hparams(opt):
 
 
 class Trainer:
+    averaged_model = None  # resolved in __init__; the engine choice reads it
+
     def __init__(self, model: nn.Module, train_dataloader, optimizer: torch.optim.Optimizer, gpu_id: int | None = None,
                  *, loss_fn=None, engine: str = "auto", graph: bool = True, comm=None,
                  snapshot_path: str | None = None, save_every: int = 0, metrics_path: str | None = None,
                  log=print, ddp_kwargs: dict | None = None, verbose: bool = True,
-                 max_grad_norm: float | None = None, lr_scheduler=None):
+                 max_grad_norm: float | None = None, lr_scheduler=None, averaged_model=None):
         self.gpu_id = env.local_rank() if gpu_id is None else gpu_id
         self.device = torch.device("cuda", self.gpu_id) if torch.cuda.is_available() else torch.device("cpu")
         self.rank = env.rank()
@@ -106,6 +112,7 @@ class Trainer:
         self.max_grad_norm = max_grad_norm
         self._clipper = None
         self.lr_scheduler = lr_scheduler  # resolved below, once the parameters are on their device
+        self.averaged_model = averaged_model  # resolved below as well
         self.snapshot_path = snapshot_path
         self.save_every = save_every
         self.epochs_run = 0
@@ -144,6 +151,8 @@ class Trainer:
                                                  comm=self.comm, **(ddp_kwargs or {}))
         if lr_scheduler is not None:
             self.lr_scheduler = self._resolve_lr_scheduler(lr_scheduler)
+        if averaged_model is not None:
+            self.averaged_model = self._resolve_averaged_model(averaged_model, model)
         if snapshot_path and os.path.exists(snapshot_path):
             self._load_snapshot(snapshot_path)
 
@@ -173,6 +182,11 @@ class Trainer:
         if self.lr_scheduler is not None:  # the fused / persistent engines take lr at plan time
             if engine in ("fused", "persistent"):
                 raise ValueError(f"{engine} engine has a fixed learning rate: lr_scheduler needs engine='autograd'")
+            if engine == "auto":
+                return "autograd"
+        if self.averaged_model is not None:  # the fused / persistent engines keep their own parameter image
+            if engine in ("fused", "persistent"):
+                raise ValueError(f"{engine} engine averages no weights: averaged_model needs engine='autograd'")
             if engine == "auto":
                 return "autograd"
         if type(self.optimizer).__name__ in ("FusedLARS", "FusedLAMB"):  # no trust ratios in those engines
@@ -205,6 +219,8 @@ class Trainer:
             self.optimizer.step()
             if self.lr_scheduler is not None:
                 self.lr_scheduler.step()
+            if self.averaged_model is not None:
+                self.averaged_model.update_parameters(self.model)
         return loss
 
     def _resolve_lr_scheduler(self, sched):
@@ -220,6 +236,17 @@ class Trainer:
         if callable(sched):
             return sched(self.optimizer)
         raise TypeError("lr_scheduler: a scheduler of ops.lr_scheduler or a callable optimizer -> scheduler")
+
+    def _resolve_averaged_model(self, avg, model):
+        """An instance (moved to the model's device), or a callable ``model -> AveragedModel`` called
+        now that the model is on its device."""
+        from ..ops.averaging import AveragedModel
+
+        if not isinstance(avg, AveragedModel) and callable(avg):
+            avg = avg(model)
+        if not isinstance(avg, AveragedModel):
+            raise TypeError("averaged_model: an ops.AveragedModel or a callable model -> AveragedModel")
+        return avg if avg.n_averaged.device == self.device else avg.to(self.device)
 
     def _clip(self):
         """Clip between backward() and step(): fused into the update for FusedSGD / FusedAdam (p.grad
@@ -373,11 +400,12 @@ class Trainer:
         if self.engine is not None:  # torch.optim.SGD layout: snapshots interchange between engines
             self.engine.export_optimizer_state(self.optimizer)
         save_checkpoint(self.snapshot_path, self.model, self.optimizer, epoch=epoch, rank=self.rank,
-                        barrier=self.comm.barrier, lr_scheduler=self.lr_scheduler)
+                        barrier=self.comm.barrier, lr_scheduler=self.lr_scheduler,
+                        averaged_model=self.averaged_model)
 
     def _load_snapshot(self, path: str):
         st = load_checkpoint(path, self.model, self.optimizer, map_location=self.device,
-                             lr_scheduler=self.lr_scheduler)
+                             lr_scheduler=self.lr_scheduler, averaged_model=self.averaged_model)
         if self.engine is not None:
             self.engine.import_optimizer_state(self.optimizer)
         self.epochs_run = int(st.get("epoch", -1)) + 1
