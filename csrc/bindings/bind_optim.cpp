@@ -35,10 +35,9 @@ void sgd_flat_(Tensor p, Tensor g, c10::optional<Tensor> mom, c10::optional<Tens
   check_gpu(g, "grad");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && p.numel() == g.numel());
   c10::hip::HIPGuard guard(p.device().index());
-  hip_check(sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), ptr_or_null<float>(mom),
-                     ptr_or_null<int32_t>(step), p.numel(), (float)lr, (float)momentum, (float)dampening,
-                     (float)wd, nesterov, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p),
-                     lr_dev_ptr(lr_dev, p)),
+  const SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, (float)grad_scale, nesterov};
+  hip_check(sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), ptr_or_null<float>(mom), ptr_or_null<int32_t>(step),
+                     p.numel(), h, gcoef_ptr(gcoef, p), lr_dev_ptr(lr_dev, p), cur_stream(p)),
             "sgd_flat");
 }
 
@@ -49,10 +48,10 @@ void adam_flat_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, double lr, 
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.numel() == p.numel() && m.numel() == p.numel() &&
               v.numel() == p.numel() && step.scalar_type() == at::kInt);
   c10::hip::HIPGuard guard(p.device().index());
+  const AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)grad_scale, decoupled};
   hip_check(adam_flat(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                      step.data_ptr<int32_t>(), p.numel(), (float)lr, (float)b1, (float)b2, (float)eps,
-                      (float)wd, decoupled, (float)grad_scale, cur_stream(p), gcoef_ptr(gcoef, p),
-                     lr_dev_ptr(lr_dev, p)),
+                      step.data_ptr<int32_t>(), p.numel(), h, gcoef_ptr(gcoef, p), lr_dev_ptr(lr_dev, p),
+                      cur_stream(p)),
             "adam_flat");
 }
 
@@ -108,39 +107,53 @@ auto adam_slots(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs, co
   };
 }
 
+// The list sizes of an SGD-shaped call. lars_multi_ needs the momentum buffers its momentum asks for
+// (sgd_multi_ takes the step without momentum when it has none).
+void check_sgd_lists(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs, const std::vector<Tensor>& moms,
+                     const std::vector<Tensor>& shadows, bool need_moms, const char* who) {
+  TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
+  TORCH_CHECK(!need_moms || !moms.empty(), who, ": momentum needs momentum buffers");
+  TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat), who,
+              ": bf16 shadows need one per (f32) param");
+}
+
+// ... and of an Adam-shaped one
+void check_adam_lists(const std::vector<Tensor>& ps, const std::vector<Tensor>& gs, const std::vector<Tensor>& ms,
+                      const std::vector<Tensor>& vs) {
+  TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
+}
+
 void sgd_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> moms,
                 c10::optional<Tensor> step, double lr, double momentum, double dampening, double wd,
                 bool nesterov, double grad_scale, std::vector<Tensor> shadows, c10::optional<Tensor> gcoef,
                 c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
-  TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
-  TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat),
-              "sgd_multi_: bf16 shadows need one per (f32) param");
+  check_sgd_lists(ps, gs, moms, shadows, false, "sgd_multi_");
   const int dt = dt_of(ps[0]);
+  const SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, (float)grad_scale, nesterov};
+  const float *gc = gcoef_ptr(gcoef, ps[0]), *lrd = lr_dev_ptr(lr_dev, ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
+  hipStream_t s = cur_stream(ps[0]);
   for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
     const TensorList tl = tensor_list(ps, gs, a, b, sgd_slots(ps, gs, moms, shadows, dt, "sgd_multi_"));
-    hip_check(sgd_multi(tl, dt, ptr_or_null<int32_t>(step), (float)lr, (float)momentum, (float)dampening,
-                        (float)wd, nesterov, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
-                        lr_dev_ptr(lr_dev, ps[0])),
-              "sgd_multi");
+    hip_check(sgd_multi(tl, dt, ptr_or_null<int32_t>(step), h, gc, lrd, s), "sgd_multi");
   });
 }
 
 void adam_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Tensor> ms,
                  std::vector<Tensor> vs, Tensor step, double lr, double b1, double b2, double eps,
                  double wd, bool decoupled, double grad_scale, c10::optional<Tensor> gcoef,
-                c10::optional<Tensor> lr_dev) {
+                 c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
-  TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
+  check_adam_lists(ps, gs, ms, vs);
   const int dt = dt_of(ps[0]);
+  const AdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)grad_scale, decoupled};
+  const float *gc = gcoef_ptr(gcoef, ps[0]), *lrd = lr_dev_ptr(lr_dev, ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
+  hipStream_t s = cur_stream(ps[0]);
   for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
     const TensorList tl = tensor_list(ps, gs, a, b, adam_slots(ps, gs, ms, vs, dt));
-    hip_check(adam_multi(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)b1, (float)b2, (float)eps,
-                         (float)wd, decoupled, (float)grad_scale, cur_stream(ps[0]), gcoef_ptr(gcoef, ps[0]),
-                        lr_dev_ptr(lr_dev, ps[0])),
-              "adam_multi");
+    hip_check(adam_multi(tl, dt, step.data_ptr<int32_t>(), h, gc, lrd, s), "adam_multi");
   });
 }
 
@@ -173,26 +186,22 @@ void lars_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
                  double trust_coefficient, double eps, std::vector<Tensor> shadows, Tensor ws, Tensor rec,
                  c10::optional<Tensor> gcoef, c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
-  TORCH_CHECK(ps.size() == gs.size() && (moms.empty() || moms.size() == ps.size()));
-  TORCH_CHECK(momentum == 0.0 || !moms.empty(), "lars_multi_: momentum needs momentum buffers");
-  TORCH_CHECK(shadows.empty() || (shadows.size() == ps.size() && ps[0].scalar_type() == at::kFloat),
-              "lars_multi_: bf16 shadows need one per (f32) param");
+  check_sgd_lists(ps, gs, moms, shadows, momentum != 0.0, "lars_multi_");
   check_layerwise(ps, step, ws, rec, "lars_multi_");
   const int dt = dt_of(ps[0]);
   const int64_t T = (int64_t)ps.size();
-  const TrustRule rule{kTrustLars, 1, (float)trust_coefficient, (float)wd, (float)eps, (float)grad_scale};
+  const SgdHyper h{(float)lr, (float)momentum, (float)dampening, (float)wd, (float)grad_scale, nesterov};
+  const TrustRule rule{kTrustLars, 1, (float)trust_coefficient, h.wd, (float)eps, h.gscale};
+  const float *gc = gcoef_ptr(gcoef, ps[0]), *lrd = lr_dev_ptr(lr_dev, ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
   hipStream_t s = cur_stream(ps[0]);
-  const float* gc = gcoef_ptr(gcoef, ps[0]);
   int64_t slot = 0;
   for_tensor_chunks(ps.size(), [&](size_t a, size_t b) {
     const TensorList tl = tensor_list(ps, gs, a, b, sgd_slots(ps, gs, moms, shadows, dt, "lars_multi_"));
     hip_check(lars_partials(tl, dt, ws.data_ptr<float>(), slot, s), "lars_partials");
     hip_check(trust_finalize(tl, ws.data_ptr<float>(), slot, rule, gc, rec.data_ptr<float>(), (int64_t)a, T, s),
               "trust_finalize");
-    hip_check(lars_update(tl, dt, step.data_ptr<int32_t>(), (float)lr, (float)momentum, (float)dampening, (float)wd,
-                          nesterov, (float)grad_scale, rec.data_ptr<float>() + a, s, gc, lr_dev_ptr(lr_dev, ps[0])),
-              "lars_update");
+    hip_check(lars_update(tl, dt, step.data_ptr<int32_t>(), h, gc, lrd, rec.data_ptr<float>() + a, s), "lars_update");
     slot += chunk_blocks(tl);
   });
 }
@@ -203,11 +212,13 @@ void lamb_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
                  Tensor step, double lr, double b1, double b2, double eps, double wd, bool bias_correction, bool adapt,
                  double grad_scale, Tensor ws, Tensor rec, c10::optional<Tensor> gcoef, c10::optional<Tensor> lr_dev) {
   if (ps.empty()) return;
-  TORCH_CHECK(ps.size() == gs.size() && ms.size() == ps.size() && vs.size() == ps.size());
+  check_adam_lists(ps, gs, ms, vs);
   check_layerwise(ps, step, ws, rec, "lamb_multi_");
   const int dt = dt_of(ps[0]);
   const int64_t T = (int64_t)ps.size();
+  const LambHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)grad_scale, bias_correction};
   const TrustRule rule{kTrustLamb, adapt ? 1 : 0, 0.f, 0.f, 0.f, 1.f};
+  const float *gc = gcoef_ptr(gcoef, ps[0]), *lrd = lr_dev_ptr(lr_dev, ps[0]);
   c10::hip::HIPGuard guard(ps[0].device().index());
   hipStream_t s = cur_stream(ps[0]);
   const int32_t* st = step.data_ptr<int32_t>();
@@ -216,14 +227,10 @@ void lamb_multi_(std::vector<Tensor> ps, std::vector<Tensor> gs, std::vector<Ten
     const TensorList tl = tensor_list(ps, gs, a, b, adam_slots(ps, gs, ms, vs, dt));
     for (size_t i = a; i < b; ++i)
       TORCH_CHECK(gs[i].scalar_type() == ps[i].scalar_type(), "lamb_multi_: a gradient of its parameter's dtype");
-    hip_check(lamb_moments(tl, dt, st, (float)b1, (float)b2, (float)eps, (float)wd, bias_correction, (float)grad_scale,
-                           ws.data_ptr<float>(), slot, s, gcoef_ptr(gcoef, ps[0])),
-              "lamb_moments");
+    hip_check(lamb_moments(tl, dt, st, h, gc, ws.data_ptr<float>(), slot, s), "lamb_moments");
     hip_check(trust_finalize(tl, ws.data_ptr<float>(), slot, rule, nullptr, rec.data_ptr<float>(), (int64_t)a, T, s),
               "trust_finalize");
-    hip_check(lamb_update(tl, dt, st, (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, bias_correction,
-                          rec.data_ptr<float>() + a, s, lr_dev_ptr(lr_dev, ps[0])),
-              "lamb_update");
+    hip_check(lamb_update(tl, dt, st, h, lrd, rec.data_ptr<float>() + a, s), "lamb_update");
     slot += chunk_blocks(tl);
   });
 }

@@ -119,13 +119,8 @@ hipError_t avg_update_multi(const AvgList& l, int src_dtype, const float* w, hip
     if (l.numel[i] < 0 || (l.numel[i] > 0 && (l.a[i] == nullptr || l.p[i] == nullptr)) ||
         (src_dtype == kF32 && l.copy[i] != nullptr))
       return hipErrorInvalidValue;
-  const int nb = chunk_blocks(l);
-  if (nb == 0) return hipSuccess;
-  if (src_dtype == kF32)
-    hipLaunchKernelGGL(avg_update_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, l, w);
-  else
-    hipLaunchKernelGGL(avg_update_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, l, w);
-  return hipGetLastError();
+  return src_dtype == kF32 ? launch_chunks(avg_update_multi_kernel<float>, kBlock, l, s, w)
+                           : launch_chunks(avg_update_multi_kernel<uint16_t>, kBlock, l, s, w);
 }
 
 hipError_t avg_update_flat(float* a, const void* p, int src_dtype, uint16_t* shadow, uint16_t* copy, int64_t numel,

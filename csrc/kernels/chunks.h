@@ -1,6 +1,7 @@
-// (tensor, chunk) block mapping of the multi-tensor launches (optim.hip, gradclip.hip):
-// the list's tensors are cut into kChunk-element chunks, one block per chunk, and a
-// block finds its tensor by a prefix search over the chunk counts in the kernel arguments.
+// (tensor, chunk) block mapping of the multi-tensor launches (optim.hip, layerwise.hip,
+// gradclip.hip, averaging.hip): the list's tensors are cut into kChunk-element chunks, one
+// block per chunk, and a block finds its tensor by a prefix search over the chunk counts in
+// the kernel arguments. launch_chunks is the host side: one block per chunk of the list.
 #pragma once
 
 #include <stdint.h>
@@ -27,6 +28,15 @@ int chunk_blocks(const L& l) {
   int b = 0;
   for (int i = 0; i < l.n; ++i) b += (int)((l.numel[i] + kChunk - 1) / kChunk);
   return b;
+}
+
+// kernel<<<chunk_blocks(l), block, 0, s>>>(l, args...); an empty list launches nothing
+template <typename K, typename L, typename... A>
+hipError_t launch_chunks(K kernel, int block, const L& l, hipStream_t s, A... args) {
+  const int nb = chunk_blocks(l);
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(block), 0, s, l, args...);
+  return hipGetLastError();
 }
 
 }  // namespace ptdt

@@ -196,35 +196,22 @@ __global__ void __launch_bounds__(kBlock) apply_spans_kernel(SpanList sl, const 
 
 template <int OP>
 hipError_t apply_spans(const SpanList& sl, int dtype, const float* rec, float c, hipStream_t s) {
-  const int nb = chunk_blocks(sl);
-  if (nb == 0) return hipSuccess;
-  if (dtype == kF32)
-    hipLaunchKernelGGL((apply_spans_kernel<float, OP>), dim3(nb), dim3(kBlock), 0, s, sl, rec, c);
-  else
-    hipLaunchKernelGGL((apply_spans_kernel<uint16_t, OP>), dim3(nb), dim3(kBlock), 0, s, sl, rec, c);
-  return hipGetLastError();
+  return dtype == kF32 ? launch_chunks(apply_spans_kernel<float, OP>, kBlock, sl, s, rec, c)
+                       : launch_chunks(apply_spans_kernel<uint16_t, OP>, kBlock, sl, s, rec, c);
 }
 
 }  // namespace
 
 hipError_t clip_norm_partials(const SpanList& sl, int dtype, int norm, float* ws, int64_t first_slot,
                               hipStream_t s) {
-  const int nb = chunk_blocks(sl);
-  if (nb == 0) return hipSuccess;
+  if (chunk_blocks(sl) == 0) return hipSuccess;  // an empty list is accepted whatever the norm
   if (norm != kClipNorm2 && norm != kClipNormInf) return hipErrorInvalidValue;
-  const dim3 grid(nb), block(kBlock);
-  if (dtype == kF32) {
-    if (norm == kClipNorm2)
-      hipLaunchKernelGGL((norm_partials_kernel<float, kClipNorm2>), grid, block, 0, s, sl, ws, first_slot);
-    else
-      hipLaunchKernelGGL((norm_partials_kernel<float, kClipNormInf>), grid, block, 0, s, sl, ws, first_slot);
-  } else {
-    if (norm == kClipNorm2)
-      hipLaunchKernelGGL((norm_partials_kernel<uint16_t, kClipNorm2>), grid, block, 0, s, sl, ws, first_slot);
-    else
-      hipLaunchKernelGGL((norm_partials_kernel<uint16_t, kClipNormInf>), grid, block, 0, s, sl, ws, first_slot);
-  }
-  return hipGetLastError();
+  auto launch = [&](auto kernel) { return launch_chunks(kernel, kBlock, sl, s, ws, first_slot); };
+  if (dtype == kF32)
+    return norm == kClipNorm2 ? launch(norm_partials_kernel<float, kClipNorm2>)
+                              : launch(norm_partials_kernel<float, kClipNormInf>);
+  return norm == kClipNorm2 ? launch(norm_partials_kernel<uint16_t, kClipNorm2>)
+                            : launch(norm_partials_kernel<uint16_t, kClipNormInf>);
 }
 
 hipError_t clip_norm_finalize(const float* ws, int64_t n, int norm, float max_norm, int partial, float* rec,

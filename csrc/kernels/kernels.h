@@ -254,20 +254,11 @@ size_t torch_perm_lds_bytes(int n);
 // Optimizers on flat buffers and multi-tensor lists (csrc/kernels/optim.hip).
 // torch.optim.SGD semantics: d = g + wd*p; buf = (first ? d : mu*buf + (1-damp)*d);
 // d = nesterov ? d + mu*buf : buf; p -= lr*d.
-// gcoef (all four): optional device float the kernel multiplies into grad_scale when it starts --
-// the gradient-clipping coefficient of gradclip.hip, applied without rewriting the gradients.
-// lr_dev (all four): optional device float that replaces lr when the kernel starts -- the group's
-// slot of a schedule's lr[G] buffer (lr_schedule.hip); AdamW's decoupled decay follows it too.
-hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
-                    float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s, const float* gcoef = nullptr,
-                    const float* lr_dev = nullptr);
-// Adam/AdamW; step is a device counter already incremented for this step.
-hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
-                     float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef = nullptr,
-                     const float* lr_dev = nullptr);
-
+// The hyper-parameters travel as the struct the kernel takes by value (grad_scale: -1 under maximize).
+// gcoef: optional device float the kernel multiplies into gscale when it starts -- the
+// gradient-clipping coefficient of gradclip.hip, applied without rewriting the gradients.
+// lr_dev: optional device float that replaces lr when the kernel starts -- the group's slot of a
+// schedule's lr[G] buffer (lr_schedule.hip); AdamW's decoupled decay follows it too.
 constexpr int kMaxTensorsPerLaunch = 32;
 struct TensorList {
   int n;                                   // tensors in this launch
@@ -278,12 +269,27 @@ struct TensorList {
   float* s2[kMaxTensorsPerLaunch];         // exp_avg_sq (f32) or nullptr; SGD on f32 params: optional bf16
                                            // shadow of the updated param (uint16_t*), the autocast weight copy
 };
-hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
-                     float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
-hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
-                      float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
+struct SgdHyper {
+  float lr, mu, damp, wd, gscale;
+  int nesterov;
+};
+struct AdamHyper {
+  float lr, b1, b2, eps, wd, gscale;
+  int decoupled;
+};
+struct LambHyper {
+  float lr, b1, b2, eps, wd, gscale;
+  int bias_correction;
+};
+hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, const SgdHyper& h,
+                    const float* gcoef, const float* lr_dev, hipStream_t s);
+// Adam/AdamW; step is a device counter already incremented for this step.
+hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
+                     const AdamHyper& h, const float* gcoef, const float* lr_dev, hipStream_t s);
+hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, const SgdHyper& h, const float* gcoef,
+                     const float* lr_dev, hipStream_t s);
+hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, const AdamHyper& h,
+                      const float* gcoef, const float* lr_dev, hipStream_t s);
 // --------------------------------------------------------------------------
 // Layer-wise adaptive rates (csrc/kernels/layerwise.hip): LARS on the SGD update, LAMB on Adam's
 // moments. Three launches per TensorList, all capturable and deterministic (no atomics, no memsets,
@@ -312,18 +318,16 @@ hipError_t lars_partials(const TensorList& tl, int dtype, float* ws, int64_t fir
 hipError_t trust_finalize(const TensorList& tl, const float* ws, int64_t first_slot, const TrustRule& r,
                           const float* gcoef, float* rec, int64_t first_tensor, int64_t tensors, hipStream_t s);
 // sgd_multi with d = ratio[t] (g' + wd p); tl as sgd_multi (s1 momentum, s2 optional bf16 shadow)
-hipError_t lars_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float momentum,
-                       float dampening, float weight_decay, int nesterov, float grad_scale, const float* ratio,
-                       hipStream_t s, const float* gcoef = nullptr, const float* lr_dev = nullptr);
+hipError_t lars_update(const TensorList& tl, int dtype, const int32_t* step, const SgdHyper& h, const float* gcoef,
+                       const float* lr_dev, const float* ratio, hipStream_t s);
 // tl as adam_multi (s1 exp_avg, s2 exp_avg_sq); step already counts this update. Updates and stores
-// m and v, writes sum p^2 and sum u^2 per chunk.
-hipError_t lamb_moments(const TensorList& tl, int dtype, const int32_t* step, float beta1, float beta2, float eps,
-                        float weight_decay, int bias_correction, float grad_scale, float* ws, int64_t first_slot,
-                        hipStream_t s, const float* gcoef = nullptr);
-// p -= lr ratio[t] u, u recomputed from the stored m, v and p by the function lamb_moments used
-hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, int bias_correction, const float* ratio, hipStream_t s,
-                       const float* lr_dev = nullptr);
+// m and v, writes sum p^2 and sum u^2 per chunk. Never reads h.lr.
+hipError_t lamb_moments(const TensorList& tl, int dtype, const int32_t* step, const LambHyper& h, const float* gcoef,
+                        float* ws, int64_t first_slot, hipStream_t s);
+// p -= lr ratio[t] u, u recomputed from the stored m, v and p by the function lamb_moments used. Never
+// reads h.gscale.
+hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, const LambHyper& h, const float* lr_dev,
+                       const float* ratio, hipStream_t s);
 
 // --------------------------------------------------------------------------
 // Weight averaging (csrc/kernels/averaging.hip): EMA / SWA of an fp32 average. All launches are

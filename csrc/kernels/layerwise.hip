@@ -25,11 +25,6 @@ constexpr int kBlock = kSgdBlock;  // kElems (chunk_elems.h) elements of a chunk
 static_assert(kBlock == kChunkThreads, "load_elems / store_elems walk a chunk with this block size");
 constexpr int kFinalBlock = 64;          // the finalise: one wave per tensor
 
-struct LambHyper {
-  float lr, b1, b2, eps, wd, gscale;
-  int bias_correction;
-};
-
 // the two sums of a thread's elements: four accumulators each, joined in a fixed order
 struct Sum2 {
   float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
@@ -237,19 +232,11 @@ __global__ void __launch_bounds__(kBlock) lars_update_kernel(TensorList tl, cons
   sgd_multi_body<T, true>(tl, step, h, gcoef, lr_dev, ratio);
 }
 
-template <typename K, typename... A>
-hipError_t launch_chunks(K kernel, const TensorList& tl, hipStream_t s, A... args) {
-  const int nb = chunk_blocks(tl);
-  if (nb == 0) return hipSuccess;
-  hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, tl, args...);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t lars_partials(const TensorList& tl, int dtype, float* ws, int64_t first_slot, hipStream_t s) {
-  return dtype == kF32 ? launch_chunks(lars_partials_kernel<float>, tl, s, ws, first_slot)
-                       : launch_chunks(lars_partials_kernel<uint16_t>, tl, s, ws, first_slot);
+  return dtype == kF32 ? launch_chunks(lars_partials_kernel<float>, kBlock, tl, s, ws, first_slot)
+                       : launch_chunks(lars_partials_kernel<uint16_t>, kBlock, tl, s, ws, first_slot);
 }
 
 hipError_t trust_finalize(const TensorList& tl, const float* ws, int64_t first_slot, const TrustRule& r,
@@ -266,28 +253,22 @@ hipError_t trust_finalize(const TensorList& tl, const float* ws, int64_t first_s
   return hipGetLastError();
 }
 
-hipError_t lars_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float momentum,
-                       float dampening, float weight_decay, int nesterov, float grad_scale, const float* ratio,
-                       hipStream_t s, const float* gcoef, const float* lr_dev) {
-  SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
-  return dtype == kF32 ? launch_chunks(lars_update_kernel<float>, tl, s, step, h, gcoef, lr_dev, ratio)
-                       : launch_chunks(lars_update_kernel<uint16_t>, tl, s, step, h, gcoef, lr_dev, ratio);
+hipError_t lars_update(const TensorList& tl, int dtype, const int32_t* step, const SgdHyper& h, const float* gcoef,
+                       const float* lr_dev, const float* ratio, hipStream_t s) {
+  return dtype == kF32 ? launch_chunks(lars_update_kernel<float>, kBlock, tl, s, step, h, gcoef, lr_dev, ratio)
+                       : launch_chunks(lars_update_kernel<uint16_t>, kBlock, tl, s, step, h, gcoef, lr_dev, ratio);
 }
 
-hipError_t lamb_moments(const TensorList& tl, int dtype, const int32_t* step, float beta1, float beta2, float eps,
-                        float weight_decay, int bias_correction, float grad_scale, float* ws, int64_t first_slot,
-                        hipStream_t s, const float* gcoef) {
-  LambHyper h{0.f, beta1, beta2, eps, weight_decay, grad_scale, bias_correction};
-  return dtype == kF32 ? launch_chunks(lamb_moments_kernel<float>, tl, s, step, h, gcoef, ws, first_slot)
-                       : launch_chunks(lamb_moments_kernel<uint16_t>, tl, s, step, h, gcoef, ws, first_slot);
+hipError_t lamb_moments(const TensorList& tl, int dtype, const int32_t* step, const LambHyper& h, const float* gcoef,
+                        float* ws, int64_t first_slot, hipStream_t s) {
+  return dtype == kF32 ? launch_chunks(lamb_moments_kernel<float>, kBlock, tl, s, step, h, gcoef, ws, first_slot)
+                       : launch_chunks(lamb_moments_kernel<uint16_t>, kBlock, tl, s, step, h, gcoef, ws, first_slot);
 }
 
-hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, int bias_correction, const float* ratio, hipStream_t s,
-                       const float* lr_dev) {
-  LambHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, bias_correction};
-  return dtype == kF32 ? launch_chunks(lamb_update_kernel<float>, tl, s, step, h, lr_dev, ratio)
-                       : launch_chunks(lamb_update_kernel<uint16_t>, tl, s, step, h, lr_dev, ratio);
+hipError_t lamb_update(const TensorList& tl, int dtype, const int32_t* step, const LambHyper& h, const float* lr_dev,
+                       const float* ratio, hipStream_t s) {
+  return dtype == kF32 ? launch_chunks(lamb_update_kernel<float>, kBlock, tl, s, step, h, lr_dev, ratio)
+                       : launch_chunks(lamb_update_kernel<uint16_t>, kBlock, tl, s, step, h, lr_dev, ratio);
 }
 
 }  // namespace ptdt

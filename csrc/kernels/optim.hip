@@ -23,11 +23,6 @@ namespace {
 
 constexpr int kBlock = kSgdBlock;
 
-struct AdamHyper {
-  float lr, b1, b2, eps, wd, gscale;
-  int decoupled;
-};
-
 // torch.optim.Adam(W) math, fp32 state.
 __device__ __forceinline__ float adam_update(float p, float g, float* m, float* v, int64_t i,
                                              float bc1, float bc2_sqrt, const AdamHyper& h) {
@@ -164,11 +159,9 @@ inline int grid_for(int64_t n, int per_thread = 4) {
 
 }  // namespace
 
-hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, float lr,
-                    float momentum, float dampening, float weight_decay, int nesterov,
-                    float grad_scale, hipStream_t s, const float* gcoef, const float* lr_dev) {
+hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t n, const SgdHyper& h,
+                    const float* gcoef, const float* lr_dev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
   hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, p, g, mom, step, n, h,
                      gcoef, lr_dev);
   if (step) hipLaunchKernelGGL(sgd_step_inc, dim3(1), dim3(1), 0, s, step);
@@ -176,70 +169,37 @@ hipError_t sgd_flat(float* p, const float* g, float* mom, int32_t* step, int64_t
 }
 
 hipError_t adam_flat(float* p, const float* g, float* m, float* v, const int32_t* step, int64_t n,
-                     float lr, float beta1, float beta2, float eps, float weight_decay,
-                     int decoupled, float grad_scale, hipStream_t s, const float* gcoef, const float* lr_dev) {
+                     const AdamHyper& h, const float* gcoef, const float* lr_dev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
   hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, p, g, m, v, step, n, h,
                      gcoef, lr_dev);
   return hipGetLastError();
 }
 
-hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, float lr, float momentum,
-                     float dampening, float weight_decay, int nesterov, float grad_scale,
-                     hipStream_t s, const float* gcoef, const float* lr_dev) {
-  const int nb = chunk_blocks(tl);
-  if (nb == 0) return hipSuccess;
-  SgdHyper h{lr, momentum, dampening, weight_decay, grad_scale, nesterov};
-  if (dtype == kF32)
-    hipLaunchKernelGGL(sgd_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
-                       lr_dev);
-  else
-    hipLaunchKernelGGL(sgd_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
-                       lr_dev);
-  return hipGetLastError();
+hipError_t sgd_multi(const TensorList& tl, int dtype, int32_t* step, const SgdHyper& h, const float* gcoef,
+                     const float* lr_dev, hipStream_t s) {
+  return dtype == kF32 ? launch_chunks(sgd_multi_kernel<float>, kBlock, tl, s, step, h, gcoef, lr_dev)
+                       : launch_chunks(sgd_multi_kernel<uint16_t>, kBlock, tl, s, step, h, gcoef, lr_dev);
 }
 
-hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, float lr, float beta1,
-                      float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
-                      hipStream_t s, const float* gcoef, const float* lr_dev) {
-  const int nb = chunk_blocks(tl);
-  if (nb == 0) return hipSuccess;
-  AdamHyper h{lr, beta1, beta2, eps, weight_decay, grad_scale, decoupled};
-  if (dtype == kF32)
-    hipLaunchKernelGGL(adam_multi_kernel<float>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
-                       lr_dev);
-  else
-    hipLaunchKernelGGL(adam_multi_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, tl, step, h, gcoef,
-                       lr_dev);
-  return hipGetLastError();
+hipError_t adam_multi(const TensorList& tl, int dtype, const int32_t* step, const AdamHyper& h,
+                      const float* gcoef, const float* lr_dev, hipStream_t s) {
+  return dtype == kF32 ? launch_chunks(adam_multi_kernel<float>, kBlock, tl, s, step, h, gcoef, lr_dev)
+                       : launch_chunks(adam_multi_kernel<uint16_t>, kBlock, tl, s, step, h, gcoef, lr_dev);
 }
 
 hipError_t bucket_pack(const CopyList& cl, void* flat, int dtype, float scale, hipStream_t s) {
-  const int nb = chunk_blocks(cl);
-  if (nb == 0) return hipSuccess;
-  if (dtype == kF32)
-    hipLaunchKernelGGL(pack_kernel<float>, dim3(nb), dim3(kBlock), 0, s, cl, (float*)flat, scale, 0);
-  else
-    hipLaunchKernelGGL(pack_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, cl, (uint16_t*)flat, scale, 0);
-  return hipGetLastError();
+  return dtype == kF32 ? launch_chunks(pack_kernel<float>, kBlock, cl, s, (float*)flat, scale, 0)
+                       : launch_chunks(pack_kernel<uint16_t>, kBlock, cl, s, (uint16_t*)flat, scale, 0);
 }
 
 hipError_t bucket_unpack(const CopyList& cl, const void* flat, int dtype, float scale, hipStream_t s) {
-  const int nb = chunk_blocks(cl);
-  if (nb == 0) return hipSuccess;
-  if (dtype == kF32)
-    hipLaunchKernelGGL(pack_kernel<float>, dim3(nb), dim3(kBlock), 0, s, cl, (float*)flat, scale, 1);
-  else
-    hipLaunchKernelGGL(pack_kernel<uint16_t>, dim3(nb), dim3(kBlock), 0, s, cl, (uint16_t*)flat, scale, 1);
-  return hipGetLastError();
+  return dtype == kF32 ? launch_chunks(pack_kernel<float>, kBlock, cl, s, (float*)flat, scale, 1)
+                       : launch_chunks(pack_kernel<uint16_t>, kBlock, cl, s, (uint16_t*)flat, scale, 1);
 }
 
 hipError_t cast_bf16_f32_multi(const TensorList& tl, hipStream_t s) {
-  const int nb = chunk_blocks(tl);
-  if (nb == 0) return hipSuccess;
-  hipLaunchKernelGGL(cast_bf16_f32_multi_kernel, dim3(nb), dim3(kBlock), 0, s, tl);
-  return hipGetLastError();
+  return launch_chunks(cast_bf16_f32_multi_kernel, kBlock, tl, s);
 }
 
 hipError_t scale_inplace(void* x, int64_t n, int dtype, float scale, hipStream_t s) {

@@ -14,11 +14,6 @@ namespace ptdt {
 
 constexpr int kSgdBlock = 256;  // threads of a multi-tensor SGD block
 
-struct SgdHyper {
-  float lr, mu, damp, wd, gscale;
-  int nesterov;
-};
-
 template <bool ADAPT = false>
 __device__ __forceinline__ float sgd_update(float p, float g, float* mom, int64_t i, bool first,
                                             const SgdHyper& h, float ratio = 1.f) {

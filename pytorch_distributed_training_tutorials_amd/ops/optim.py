@@ -27,6 +27,8 @@ names, per-parameter state keys ``momentum_buffer`` / ``exp_avg`` /
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 from torch.optim import Optimizer
 
@@ -144,7 +146,69 @@ class _DeviceLr:
         return views[gi]
 
 
-class FusedSGD(_GradCoef, _DeviceLr, Optimizer):
+# What one update launches over: the parameters of one (group, device, dtype) that share a step counter
+# (None where the class keeps none: FusedSGD on the CPU), with the operands step() looked up for them.
+_Cohort = namedtuple("_Cohort", "gi group device dtype params step gcoef lr_dev")
+
+
+def _gscale(group) -> float:
+    return -1.0 if group["maximize"] else 1.0
+
+
+def _effective(c, g):
+    """The gradient the CPU updates see: ``maximize``'s sign and the armed clip coefficient applied."""
+    g = g * _gscale(c.group)
+    return g if c.gcoef is None else g * c.gcoef
+
+
+# The scalars the SGD-shaped and the Adam-shaped bindings share, in the bindings' order: they go by position
+# (wrappers around the four older bindings read operands by index), the rest of lars_multi_ / lamb_multi_ by keyword.
+def _sgd_hyper(group) -> tuple:
+    return (group["lr"], group["momentum"], group["dampening"], group["weight_decay"], group["nesterov"],
+            _gscale(group))
+
+
+def _adam_hyper(group) -> tuple:
+    return (group["lr"], *group["betas"], group["eps"], group["weight_decay"])
+
+
+class _FusedOptimizer(_GradCoef, _DeviceLr, Optimizer):
+    """The one ``step()`` of the fused optimizers: closure, grad coefficients, then per group and
+    (device, dtype) the operands and the cohorts, each handed to the class's CPU or GPU update.
+    Subclasses say what a new parameter's count starts at (:meth:`_initial_count`), whether CPU
+    parameters are counted (``_counts_cpu``), and supply :meth:`_gpu_update` / :meth:`_cpu_update`."""
+
+    _counts_cpu = True
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._cohorts = _StepCounters()
+
+    @property
+    def _counters(self) -> dict:
+        """The live device counters (a counter reads 0 until its cohort's first update)."""
+        return self._cohorts.counters
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        coefs = self._take_grad_coef()
+        for gi, group in enumerate(self.param_groups):
+            for (device, dtype), ps in _split_by_device(group["params"]).items():
+                gcoef, lr_dev = coefs.get(device), self._lr_dev(gi, device)
+                on_gpu = device.type == "cuda"
+                update = self._gpu_update if on_gpu else self._cpu_update
+                # before any state buffer is created: a parameter's first step is decided here
+                counted = on_gpu or self._counts_cpu
+                for step, cps in self._cohorts.cohorts(ps, self._initial_count) if counted else [(None, ps)]:
+                    update(_Cohort(gi, group, device, dtype, cps, step, gcoef, lr_dev))
+        return loss
+
+
+class FusedSGD(_FusedOptimizer):
     """``bf16_shadow=True``: every f32 GPU parameter also gets a bf16 copy of its
     updated value, written by the same update kernel (``p._ptdt_bf16``); under bf16
     autocast :func:`ops.conv.cast_weight` uses it instead of casting the weight in
@@ -160,19 +224,15 @@ class FusedSGD(_GradCoef, _DeviceLr, Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                         nesterov=nesterov, maximize=maximize)
         super().__init__(params, defaults)
-        self._cohorts = _StepCounters()
         self.bf16_shadow = bf16_shadow
 
-    @property
-    def _counters(self) -> dict:
-        """The live device counters (a counter reads 0 until its cohort's first update)."""
-        return self._cohorts.counters
+    _counts_cpu = False  # on the CPU the first step is decided by the presence of ``momentum_buffer``
 
-    def _started(self, p) -> int:
+    def _initial_count(self, p) -> int:
         """1 when a parameter new to this optimizer object already has a (loaded) momentum buffer."""
         return int("momentum_buffer" in self.state[p])
 
-    def _momentum_buffers(self, gi, ps):
+    def _momentum_buffers(self, ps):
         """Per-parameter momentum buffers; for flat parameter spans they are views
         of one flat buffer so the update stays a single launch."""
         if all("momentum_buffer" in self.state[p] for p in ps):
@@ -190,55 +250,42 @@ class FusedSGD(_GradCoef, _DeviceLr, Optimizer):
             off += p.numel()
         return out
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        coefs = self._take_grad_coef()
-        for gi, group in enumerate(self.param_groups):
-            lr, mu, damp, wd, nest = (group["lr"], group["momentum"], group["dampening"],
-                                      group["weight_decay"], group["nesterov"])
-            gscale = -1.0 if group["maximize"] else 1.0
-            for (device, dtype), ps in _split_by_device(group["params"]).items():
-                gcoef = coefs.get(device)
-                if device.type != "cuda":
-                    self._cpu_step(ps, lr, mu, damp, wd, nest, gscale, gcoef)
-                    continue
-                lr_dev = self._lr_dev(gi, device)
-                # before creating buffers: a parameter's "first step" is decided here
-                for step, cps in self._cohorts.cohorts(ps, self._started):
-                    self._gpu_step(gi, cps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
-        return loss
-
-    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None, lr_dev=None):
+    def _gpu_update(self, c):
+        ps = c.params
         grads = [p.grad for p in ps]
-        moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
-        C = native()
-        pflat = contiguous_span([p.data for p in ps])
-        gflat = contiguous_span(grads)
-        mflat = contiguous_span(moms) if moms else None
-        pdata = [p.data for p in ps]
-        aligned = same_layout(pdata, grads) and (not moms or same_layout(pdata, moms))
-        shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and dtype == torch.float32) else []
-        if (dtype == torch.float32 and aligned and pflat is not None and gflat is not None
-                and (not moms or mflat is not None) and not shadows):
-            # one launch for the whole cohort (also increments the device counter)
-            C.sgd_flat_(pflat, gflat, mflat, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
-        else:
-            C.sgd_multi_(pdata, grads, moms, step, lr, mu, damp, wd, nest, gscale, shadows, gcoef, lr_dev)
-            step.add_(1)
+        moms = self._momentum_buffers(ps) if c.group["momentum"] != 0.0 else []
+        shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and c.dtype == torch.float32) else []
+        self._launch(c, grads, moms, shadows)
         for p in ps if shadows else ():
             p._ptdt_bf16_version = p._version  # the shadow is current until p changes
 
-    def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale, gcoef=None):
-        for p in ps:
-            d = p.grad * gscale
-            if gcoef is not None:
-                d = d * gcoef
-            if wd != 0:
-                d = d.add(p, alpha=wd)
+    def _launch(self, c, grads, moms, shadows):
+        """One flat launch when the cohort is one aligned f32 span (it also advances the counter),
+        else the multi-tensor form, the counter advanced after it."""
+        pdata = [p.data for p in c.params]
+        hyper = _sgd_hyper(c.group)
+        if c.dtype == torch.float32 and not shadows and same_layout(pdata, grads) and (
+                not moms or same_layout(pdata, moms)):
+            pflat, gflat = contiguous_span(pdata), contiguous_span(grads)
+            mflat = contiguous_span(moms) if moms else None
+            if pflat is not None and gflat is not None and (not moms or mflat is not None):
+                return native().sgd_flat_(pflat, gflat, mflat, c.step, *hyper, c.gcoef, c.lr_dev)
+        native().sgd_multi_(pdata, grads, moms, c.step, *hyper, shadows, c.gcoef, c.lr_dev)
+        c.step.add_(1)
+
+    def _cpu_ratio(self, group, p, g):
+        """The factor on the decayed gradient before the momentum step: none for plain SGD."""
+        return None
+
+    def _cpu_update(self, c):
+        group = c.group
+        lr, mu, damp, wd = group["lr"], group["momentum"], group["dampening"], group["weight_decay"]
+        for p in c.params:
+            g = _effective(c, p.grad)
+            ratio = self._cpu_ratio(group, p, g)
+            d = g.add(p, alpha=wd) if wd != 0 else g
+            if ratio is not None:
+                d = d * ratio.to(d.dtype)
             if mu != 0:
                 buf = self.state[p].get("momentum_buffer")
                 if buf is None:
@@ -246,11 +293,11 @@ class FusedSGD(_GradCoef, _DeviceLr, Optimizer):
                     self.state[p]["momentum_buffer"] = buf
                 else:
                     buf.mul_(mu).add_(d, alpha=1 - damp)
-                d = d.add(buf, alpha=mu) if nest else buf
+                d = d.add(buf, alpha=mu) if group["nesterov"] else buf
             p.add_(d, alpha=-lr)
 
 
-class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
+class FusedAdam(_FusedOptimizer):
     """Adam / AdamW (``decoupled_weight_decay=True``) with fp32 state."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -258,9 +305,8 @@ class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                         decoupled_weight_decay=decoupled_weight_decay, maximize=maximize)
         super().__init__(params, defaults)
-        self._cohorts = _StepCounters()
 
-    def _loaded_step(self, p) -> int:
+    def _initial_count(self, p) -> int:
         """Updates a parameter new to this optimizer object already has behind it (a loaded state)."""
         return int(float(self.state[p].get("step", 0)))
 
@@ -277,38 +323,24 @@ class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
                 off += p.numel()
         return [self.state[p]["exp_avg"] for p in ps], [self.state[p]["exp_avg_sq"] for p in ps]
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        coefs = self._take_grad_coef()
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
-            gscale = -1.0 if group["maximize"] else 1.0
-            for (device, dtype), sub in _split_by_device(group["params"]).items():
-                gcoef = coefs.get(device)
-                lr_dev = self._lr_dev(gi, device)
-                for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
-                    step.add_(1)
-                    ms, vs = self._state_lists(ps)
-                    if device.type != "cuda":
-                        self._cpu_step(ps, ms, vs, step, group, gscale, gcoef)
-                        continue
-                    C = native()
-                    grads = [p.grad for p in ps]
-                    pflat, gflat = contiguous_span([p.data for p in ps]), contiguous_span(grads)
-                    mflat, vflat = contiguous_span(ms), contiguous_span(vs)
-                    pdata = [p.data for p in ps]
-                    aligned = same_layout(pdata, grads) and same_layout(pdata, ms) and same_layout(pdata, vs)
-                    if dtype == torch.float32 and aligned and None not in (pflat, gflat, mflat, vflat):
-                        C.adam_flat_(pflat, gflat, mflat, vflat, step, group["lr"], b1, b2, group["eps"],
-                                     group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef, lr_dev)
-                    else:
-                        C.adam_multi_(pdata, grads, ms, vs, step, group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], group["decoupled_weight_decay"], gscale, gcoef, lr_dev)
-        return loss
+    def _advance(self, c):
+        """Counts this update (CPU and GPU cohorts alike, ahead of the update), then the moments."""
+        c.step.add_(1)
+        return self._state_lists(c.params)
+
+    def _gpu_update(self, c):
+        ms, vs = self._advance(c)
+        self._launch(c, [p.grad for p in c.params], ms, vs)
+
+    def _launch(self, c, grads, ms, vs):
+        """One flat launch when parameters, gradients and moments are aligned f32 spans, else multi-tensor."""
+        pdata = [p.data for p in c.params]
+        tail = (*_adam_hyper(c.group), c.group["decoupled_weight_decay"], _gscale(c.group), c.gcoef, c.lr_dev)
+        if c.dtype == torch.float32 and all(same_layout(pdata, ts) for ts in (grads, ms, vs)):
+            flat = [contiguous_span(ts) for ts in (pdata, grads, ms, vs)]
+            if all(t is not None for t in flat):
+                return native().adam_flat_(*flat, c.step, *tail)
+        native().adam_multi_(pdata, grads, ms, vs, c.step, *tail)
 
     def state_dict(self):
         """torch.optim.Adam layout: per parameter ``exp_avg``, ``exp_avg_sq`` and the
@@ -319,7 +351,7 @@ class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
                 if p in self.state:
                     step = self._cohorts.count(p)
                     self.state[p]["step"] = torch.tensor(float(step.item()) if step is not None
-                                                         else float(self._loaded_step(p)))
+                                                         else float(self._initial_count(p)))
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
@@ -344,25 +376,30 @@ class FusedAdam(_GradCoef, _DeviceLr, Optimizer):
                             m.copy_(loaded[p][0])
                             v.copy_(loaded[p][1])
 
-    @staticmethod
-    def _cpu_step(ps, ms, vs, step, group, gscale, gcoef=None):
-        t = float(step.item())
+    def _cpu_update(self, c):
+        ms, vs = self._advance(c)
+        group = c.group
         b1, b2 = group["betas"]
-        lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
-        bc1 = 1 - b1 ** t
-        bc2s = (1 - b2 ** t) ** 0.5
-        for p, m, v in zip(ps, ms, vs):
-            g = p.grad.float() * gscale
-            if gcoef is not None:
-                g = g * gcoef
-            if group["decoupled_weight_decay"]:
-                p.mul_(1 - lr * wd)
-            elif wd != 0:
-                g = g.add(p, alpha=wd)
+        t = float(c.step.item())
+        correct = group.get("bias_correction", True)
+        bc1 = 1 - b1 ** t if correct else 1.0
+        bc2s = (1 - b2 ** t) ** 0.5 if correct else 1.0
+        for p, m, v in zip(c.params, ms, vs):
+            g = self._cpu_decay(group, p, _effective(c, p.grad.float()))
             m.mul_(b1).add_(g, alpha=1 - b1)
             v.mul_(b2).addcmul_(g, g, value=1 - b2)
-            denom = v.sqrt() / bc2s + eps
-            p.addcdiv_(m, denom, value=-lr / bc1)
+            self._cpu_apply(group, p, m, v.sqrt() / bc2s + group["eps"], bc1)
+
+    def _cpu_decay(self, group, p, g):
+        """Adam's weight decay, ahead of the moments: on the parameter (AdamW) or into the gradient."""
+        if group["decoupled_weight_decay"]:
+            p.mul_(1 - group["lr"] * group["weight_decay"])
+        elif group["weight_decay"] != 0:
+            g = g.add(p, alpha=group["weight_decay"])
+        return g
+
+    def _cpu_apply(self, group, p, m, denom, bc1):
+        p.addcdiv_(m, denom, value=-group["lr"] / bc1)
 
 
 # ---------------------------------------------------------------------------- layer-wise rates
@@ -393,16 +430,21 @@ class _TrustRatios:
         self._trust_plans: dict = {}  # (group index, id of the cohort's counter) -> (counter, _TrustPlan)
         self._trust_cpu: dict = {}    # CPU parameters: parameter -> (ratio, w, n)
 
-    def _trust_plan(self, gi, step, ps, grads) -> _TrustPlan:
+    def _trust_plan(self, c, grads) -> _TrustPlan:
+        ps, at = c.params, (c.gi, id(c.step))
         key = [(p.data_ptr(), g.data_ptr(), p.numel()) for p, g in zip(ps, grads)]
-        held = self._trust_plans.get((gi, id(step)))
+        held = self._trust_plans.get(at)
         if held is not None and held[1].key == key:
             return held[1]
         plan = _TrustPlan(ps, key)
         mine = set(ps)  # a parameter reports through one plan: drop the plans it has left
         self._trust_plans = {k: v for k, v in self._trust_plans.items() if mine.isdisjoint(v[1].params)}
-        self._trust_plans[(gi, id(step))] = (step, plan)  # holding the counter keeps its id unique
+        self._trust_plans[at] = (c.step, plan)  # holding the counter keeps its id unique
         return plan
+
+    def _record_cpu(self, p, ratio, w, n):
+        self._trust_cpu[p] = (float(ratio), float(w), float(n))
+        return ratio
 
     def trust_ratios(self) -> dict:
         """``{parameter: (ratio, w, n)}`` as the latest update of each parameter computed them:
@@ -463,44 +505,23 @@ class FusedLARS(_TrustRatios, FusedSGD):
         super().load_state_dict(state_dict)
         self._restore_group_keys(before)
 
-    def _gpu_step(self, gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef=None, lr_dev=None):
-        group = self.param_groups[gi]
+    def _launch(self, c, grads, moms, shadows):
+        group = c.group
         if group["trust_coefficient"] == 0:
-            return super()._gpu_step(gi, ps, dtype, step, lr, mu, damp, wd, nest, gscale, gcoef, lr_dev)
-        grads = [p.grad for p in ps]
-        moms = self._momentum_buffers(gi, ps) if mu != 0.0 else []
-        shadows = [_bf16_shadow(p) for p in ps] if (self.bf16_shadow and dtype == torch.float32) else []
-        plan = self._trust_plan(gi, step, ps, grads)
-        native().lars_multi_([p.data for p in ps], grads, moms, step, lr, mu, damp, wd, nest, gscale,
-                             group["trust_coefficient"], group["eps"], shadows, plan.ws, plan.rec, gcoef, lr_dev)
-        step.add_(1)
-        for p in ps if shadows else ():
-            p._ptdt_bf16_version = p._version  # the shadow is current until p changes
+            return super()._launch(c, grads, moms, shadows)
+        plan = self._trust_plan(c, grads)
+        native().lars_multi_([p.data for p in c.params], grads, moms, c.step, *_sgd_hyper(group),
+                             trust_coefficient=group["trust_coefficient"], eps=group["eps"], shadows=shadows,
+                             ws=plan.ws, rec=plan.rec, gcoef=c.gcoef, lr_dev=c.lr_dev)
+        c.step.add_(1)
 
-    def _cpu_step(self, ps, lr, mu, damp, wd, nest, gscale, gcoef=None):
-        # FusedSGD.step hands the CPU path no group: find the one these parameters belong to
-        group = next(g for g in self.param_groups if any(q is ps[0] for q in g["params"]))
-        tc, eps = group["trust_coefficient"], group["eps"]
+    def _cpu_ratio(self, group, p, g):
+        tc, wd = group["trust_coefficient"], group["weight_decay"]
         if tc == 0:
-            return super()._cpu_step(ps, lr, mu, damp, wd, nest, gscale, gcoef)
-        for p in ps:
-            g = p.grad * gscale
-            if gcoef is not None:
-                g = g * gcoef
-            w, n = _norm64(p), _norm64(g)
-            ratio = tc * w / (n + wd * w + eps) if (w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
-            self._trust_cpu[p] = (float(ratio), float(w), float(n))
-            d = g.add(p, alpha=wd) if wd != 0 else g
-            d = d * ratio.to(d.dtype)
-            if mu != 0:
-                buf = self.state[p].get("momentum_buffer")
-                if buf is None:
-                    buf = d.clone()
-                    self.state[p]["momentum_buffer"] = buf
-                else:
-                    buf.mul_(mu).add_(d, alpha=1 - damp)
-                d = d.add(buf, alpha=mu) if nest else buf
-            p.add_(d, alpha=-lr)
+            return None
+        w, n = _norm64(p), _norm64(g)
+        ratio = tc * w / (n + wd * w + group["eps"]) if (w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
+        return self._record_cpu(p, ratio, w, n)
 
 
 class FusedLAMB(_TrustRatios, FusedAdam):
@@ -535,51 +556,24 @@ class FusedLAMB(_TrustRatios, FusedAdam):
         super().load_state_dict(state_dict)
         self._restore_group_keys(before)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        coefs = self._take_grad_coef()
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
-            gscale = -1.0 if group["maximize"] else 1.0
-            for (device, dtype), sub in _split_by_device(group["params"]).items():
-                gcoef = coefs.get(device)
-                lr_dev = self._lr_dev(gi, device)
-                for step, ps in self._cohorts.cohorts(sub, self._loaded_step):
-                    step.add_(1)
-                    ms, vs = self._state_lists(ps)
-                    if device.type != "cuda":
-                        self._cpu_step(ps, ms, vs, step, group, gscale, gcoef)
-                        continue
-                    grads = [p.grad for p in ps]
-                    plan = self._trust_plan(gi, step, ps, grads)
-                    native().lamb_multi_([p.data for p in ps], grads, ms, vs, step, group["lr"], b1, b2,
-                                         group["eps"], group["weight_decay"], group["bias_correction"],
-                                         group["adapt"], gscale, plan.ws, plan.rec, gcoef, lr_dev)
-        return loss
+    def _launch(self, c, grads, ms, vs):
+        group = c.group
+        plan = self._trust_plan(c, grads)
+        native().lamb_multi_([p.data for p in c.params], grads, ms, vs, c.step, *_adam_hyper(group),
+                             bias_correction=group["bias_correction"], adapt=group["adapt"],
+                             grad_scale=_gscale(group), ws=plan.ws, rec=plan.rec, gcoef=c.gcoef, lr_dev=c.lr_dev)
 
-    def _cpu_step(self, ps, ms, vs, step, group, gscale, gcoef=None):
-        t = float(step.item())
-        b1, b2 = group["betas"]
-        lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
-        bc1 = 1 - b1 ** t if group["bias_correction"] else 1.0
-        bc2s = (1 - b2 ** t) ** 0.5 if group["bias_correction"] else 1.0
-        for p, m, v in zip(ps, ms, vs):
-            g = p.grad.float() * gscale
-            if gcoef is not None:
-                g = g * gcoef
-            m.mul_(b1).add_(g, alpha=1 - b1)
-            v.mul_(b2).addcmul_(g, g, value=1 - b2)
-            u = (m / bc1) / (v.sqrt() / bc2s + eps)
-            if wd != 0:
-                u = u.add(p, alpha=wd)
-            w, n = _norm64(p), _norm64(u)
-            ratio = w / n if (group["adapt"] and w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
-            self._trust_cpu[p] = (float(ratio), float(w), float(n))
-            p.add_(u.to(p.dtype), alpha=-lr * float(ratio))
+    def _cpu_decay(self, group, p, g):
+        return g  # LAMB decays in the direction, not in the gradient
+
+    def _cpu_apply(self, group, p, m, denom, bc1):
+        u = (m / bc1) / denom
+        if group["weight_decay"] != 0:
+            u = u.add(p, alpha=group["weight_decay"])
+        w, n = _norm64(p), _norm64(u)
+        ratio = w / n if (group["adapt"] and w > 0 and n > 0) else torch.ones((), dtype=torch.float64)
+        self._record_cpu(p, ratio, w, n)
+        p.add_(u.to(p.dtype), alpha=-group["lr"] * float(ratio))
 
 
 def layerwise_param_groups(module: torch.nn.Module, weight_decay: float = 0.0, **adapt_off) -> list:
