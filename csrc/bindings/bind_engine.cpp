@@ -537,6 +537,45 @@ void bind_engine(py::module_& m) {
         return py::make_tuple(ofs, flags, slots, barriers, estride);
       },
       py::arg("S"), py::arg("B"), py::arg("e0"), py::arg("j0"), py::arg("n"), py::arg("depth") = kWavePrefetch);
+  // Run length of the lean wave loop from one state (ij reads made in the list, ring slot rslot,
+  // groups_left whole groups left in the launch), and the state after advance(run):
+  // (run, ij, lofs, rslot), with lofs counted from ij * B.
+  m.def(
+      "wave_loop_run_length",
+      [](int S, int B, int depth, int ring, int ij, int rslot, int groups_left) {
+        TORCH_CHECK(S > 0 && B > 0 && depth > 0 && ring > depth && ij >= 0 && ij <= S && rslot >= 0 && rslot < ring &&
+                        groups_left >= 0,
+                    "wave_loop_run_length: bad arguments");
+        WaveLoopSchedule s;
+        s.init(S, B, wave_list_stride(S * B, B), 0, 0, 0, depth, ring);
+        s.ij = ij;
+        s.lofs = ij * B;
+        s.rslot = rslot;
+        const int r = s.run(groups_left);
+        s.advance(r);
+        return py::make_tuple(r, s.ij, s.lofs, s.rslot);
+      },
+      py::arg("S"), py::arg("B"), py::arg("depth"), py::arg("ring"), py::arg("ij"), py::arg("rslot"),
+      py::arg("groups_left"));
+  // wave_loop_check_runs over every start j0 of an epoch of S batches and every launch length
+  // 0..n_max, ring = 2 S + depth: (launches, group boundaries checked, first launch that differs as
+  // (j0, n) or None).
+  m.def(
+      "wave_loop_check_runs",
+      [](int S, int B, int depth, int n_max) {
+        TORCH_CHECK(S > 0 && B > 0 && depth > 0 && n_max >= 0, "wave_loop_check_runs: bad arguments");
+        const int estride = wave_list_stride(S * B, B), ring = 2 * S + depth;
+        int64_t launches = 0, boundaries = 0;
+        for (int j0 = 0; j0 < S; ++j0)
+          for (int n = 0; n <= n_max; ++n) {
+            const long c = wave_loop_check_runs(S, B, estride, j0 & 1, j0, n, depth, ring);
+            if (c < 0) return py::make_tuple(launches, boundaries, py::cast(std::make_pair(j0, n)));
+            ++launches;
+            boundaries += c;
+          }
+        return py::make_tuple(launches, boundaries, py::object(py::none()));
+      },
+      py::arg("S"), py::arg("B"), py::arg("depth"), py::arg("n_max"));
 
   // Row image of the wave engine (wave_row_image.h). wave_row_image_layout(Din, KP): (floats per
   // record RS, bytes per row, slot of 1.0f or -1, slot of y, source[q][s] of every record slot: a

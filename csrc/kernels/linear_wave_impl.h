@@ -1072,6 +1072,10 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
   if constexpr ((KP & 1) != 0) x[KP - 1] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off + 4 * (KP - 1), 0, 0));
 }
 
+// Whether a lean kernel's step loop has two unrolled group bodies or one (defined next to the
+// instantiation table below).
+constexpr bool lean_two_bodies(int R, int KP, int DOUT, int var, bool ar);
+
 // VAR (WaveKernelVariant, chosen per plan by linear_wave_variant): the generic kernel decides the SGD
 // kind, the loss path, the row masks and the stamps at run time. A lean variant (kWaveLeanPlain /
 // kWaveLeanMom) is the same kernel with the plan's facts as constants -- that SGD kind, the loss ring
@@ -1086,8 +1090,12 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
 //                     no wrap, barrier or ring test; the list entries (lp, lp_y) and the ring slot (rp)
 //                     are running per-lane addresses; one wait per batch, where the step first
 //                     touches it;
-//   checked group   : the same body under a uniform flag: every step is followed by a checked read
-//                     (list switch, epoch barrier, address reset) and a checked ring slot;
+//   checked group   : every step is followed by a checked read (list switch, epoch barrier, address
+//                     reset) and a checked ring slot;
+//   runs            : where the registers hold two group bodies (lean_two_bodies), the unchecked
+//                     groups run in a loop of their own under a down-counter (the schedule's run
+//                     length) and the checked group that follows a run has its own body; else both
+//                     kinds share one body under a uniform per-group flag;
 //   loss share      : stored raw; reduce_losses in the helper waves applies the owner mask and the
 //                     1/rows scale per share, in the trainer's order, before its fixed-order sum;
 //   barriers        : T epoch barriers + the final one whatever the loop did (topped up after the loop).
@@ -1814,40 +1822,68 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // one loop instantiation per (SGD kind, loss ring): no per-step branch on either. Plain SGD (the
   // reference's SGD(lr)) has its own loop with the ring only; without the ring it takes the
   // weight-decay loop (same values: d = g + 0 * w).
-  // lean: one unrolled group body (three register buffers in turn). Unchecked, a step is followed by
-  // a read at the running address; checked (a uniform per-group flag), by a checked read and ring slot.
+  // lean: unrolled group bodies (three register buffers in turn). Two of them where the registers
+  // hold both (lean_two_bodies): a run of unchecked groups is train, gather, read at the running
+  // address, kNB times, under a down-counter and nothing else; a checked group follows every step with a
+  // checked read and ring slot. Otherwise one body under a uniform per-group flag.
   // The n % kNB steps after the last group gather nothing.
+  auto lean_tail = [&](WaveLoopSchedule& c, int left, auto sgd_tag) {
+    int k = 0;
+#pragma unroll
+    for (int u = 0; u < kNB - 1; ++u) {
+      if (u < left && !failed) {
+        train(buf[u], 0, sgd_tag, std::true_type{});
+        if (c.slot_done()) rp = lring + lane;
+        ++k;
+      }
+    }
+    return k;
+  };
   auto run_lean = [&](auto sgd_tag) {
     if (failed) return;
-    done = wave_loop_run(
-        sch, n,
-        [&](WaveLoopSchedule& c, bool checked) {
+    if constexpr (lean_two_bodies(R, KP, DOUT, VAR, AR)) {
+      done = wave_loop_run(
+          sch, n,
+          [&]() {
 #pragma unroll
-          for (int u = 0; u < kNB; ++u) {
-            train(buf[u], 0, sgd_tag, std::true_type{});
-            load_batch(buf[u], sel_next, sel_y_next, B);
-            if (__builtin_expect(checked, 0)) {  // laid out behind the loop: the unchecked path falls through
-              read_checked();
-              if (c.slot_done()) rp = lring + lane;
-            } else {
+            for (int u = 0; u < kNB; ++u) {
+              train(buf[u], 0, sgd_tag, std::true_type{});
+              load_batch(buf[u], sel_next, sel_y_next, B);
               read_run();
             }
-          }
-          if (!checked) c.advance();
-          return !failed;
-        },
-        [&](WaveLoopSchedule& c, int left) {
-          int k = 0;
+            return !failed;
+          },
+          [&](WaveLoopSchedule& c) {
 #pragma unroll
-          for (int u = 0; u < kNB - 1; ++u) {
-            if (u < left && !failed) {
+            for (int u = 0; u < kNB; ++u) {
               train(buf[u], 0, sgd_tag, std::true_type{});
+              load_batch(buf[u], sel_next, sel_y_next, B);
+              read_checked();
               if (c.slot_done()) rp = lring + lane;
-              ++k;
             }
-          }
-          return k;
-        });
+            return !failed;
+          },
+          [&](WaveLoopSchedule& c, int left) { return lean_tail(c, left, sgd_tag); });
+    } else {
+      done = wave_loop_run_flagged(
+          sch, n,
+          [&](WaveLoopSchedule& c, bool checked) {
+#pragma unroll
+            for (int u = 0; u < kNB; ++u) {
+              train(buf[u], 0, sgd_tag, std::true_type{});
+              load_batch(buf[u], sel_next, sel_y_next, B);
+              if (__builtin_expect(checked, 0)) {  // laid out behind the loop: the unchecked path falls through
+                read_checked();
+                if (c.slot_done()) rp = lring + lane;
+              } else {
+                read_run();
+              }
+            }
+            if (!checked) c.advance();
+            return !failed;
+          },
+          [&](WaveLoopSchedule& c, int left) { return lean_tail(c, left, sgd_tag); });
+    }
   };
   using Plain = std::integral_constant<int, kSgdPlain>;
   using NoMom = std::integral_constant<int, kSgdNoMom>;
@@ -1915,6 +1951,18 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the final stores issued above are done
     tl_mark(tl_p, 3);
   }
+}
+
+// Two unrolled group bodies hold the kNB batch buffers (R KP values each, a row record or features
+// and targets) live across both, next to DOUT KP weights (and momenta). Built with two bodies
+// everywhere (tools/wave_kernel_resources.py, profiles/wave_loop_runs.md): every R == 4 kernel ends
+// within a few registers of the 256 or past them (copies through accumulation registers; <4,16,1>
+// gains 88 to 644 bytes of scratch), <2,16,1> and most all-reduce kernels of two outputs or KP >= 8
+// likewise, or they spill already and would carry the spill code twice. Those keep one body under
+// the per-group flag. The rule holds for both lean variants and every loss: `var` does not enter it.
+constexpr bool lean_two_bodies(int R, int KP, int DOUT, int var, bool ar) {
+  (void)var;
+  return ar ? (DOUT == 1 && R <= 2 && KP <= 5) : (R <= 2 && R * KP * DOUT <= 20);
 }
 
 // Instantiation table of one loss and all-reduce flag: (L, R, KP, DOUT)
