@@ -90,6 +90,10 @@ def main(argv=None):
                          "optimizer step: ops.AveragedModel (native; no host read, captured with the step, bf16 "
                          "shadows like the optimizer's) or torch.optim.swa_utils.AveragedModel (--impl torch). "
                          "Default: off")
+    ap.add_argument("--eval_steps", type=int, default=0, metavar="N",
+                    help="after the timed region, evaluate N held synthetic batches on the model (and on the --ema "
+                         "copy) with ops.ClassificationMeter: adds eval_top1, eval_loss and eval_ms_per_batch to the "
+                         "JSON line. Default 0: off")
     a = ap.parse_args(argv)
     if a.optimizer != "sgd" and a.impl == "torch":
         ap.error(f"--optimizer {a.optimizer} has no stock torch comparator: use --impl native")
@@ -288,6 +292,47 @@ def main(argv=None):
         f = torch.tensor([1.0 if finite else 0.0], device=dev)
         comm.all_reduce(f, "min")
         finite = bool(f.item() == 1.0)
+    evals = {}
+    if a.eval_steps > 0 and finite:  # outside the timed region; every rank takes part in compute(comm)
+        from pytorch_distributed_training_tutorials_amd.ops import ClassificationMeter
+
+        held = []  # batches the training never saw: other Philox streams, labels from another seed
+        gen = torch.Generator(device=dev).manual_seed(4321 + rank)
+        for i in range(a.eval_steps):
+            xe = torch.empty(a.batch_size, 3, a.image, a.image, device=dev)
+            native().philox_(xe, 98765 + rank, i + 1, 1)
+            if not a.no_channels_last:
+                xe = xe.contiguous(memory_format=torch.channels_last)
+            held.append((xe, torch.randint(0, 1000, (a.batch_size,), device=dev, generator=gen)))
+
+        def evaluate(net):
+            """(metrics, ms per batch): eval mode, no_grad, the training's autocast; one host read at the end."""
+            meter = ClassificationMeter((1, 5), device=dev)
+            modes = [(m, m.training) for m in net.modules()]
+            net.eval()
+            with torch.no_grad():
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    net(held[0][0])  # untimed: the eval-mode solvers and kernels load here
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for xe, ye in held:
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                        out = net(xe)
+                    meter.update(out, ye)
+            torch.cuda.synchronize(dev)
+            ms = 1e3 * (time.perf_counter() - t0) / len(held)
+            for m, flag in modes:
+                m.training = flag
+            return meter.compute(comm), ms
+
+        res, ms = evaluate(model)
+        evals = {"eval_steps": a.eval_steps, "eval_top1": res["top1"], "eval_top5": res["top5"],
+                 "eval_loss": res["loss"], "eval_count": res["count"], "eval_nonfinite": res["nonfinite"],
+                 "eval_ms_per_batch": round(ms, 3)}
+        if ema is not None:
+            res, ms = evaluate(ema)
+            evals.update(eval_ema_top1=res["top1"], eval_ema_top5=res["top5"], eval_ema_loss=res["loss"],
+                         eval_ema_ms_per_batch=round(ms, 3))
     if rank == 0 and not finite:
         print(json.dumps({"metric": "ResNet-50 DDP training throughput (whole node)", "value": None,
                           "error": f"non-finite training loss {final} after {executed + a.steps} steps: no throughput "
@@ -315,6 +360,7 @@ def main(argv=None):
             **({"ema_decay": a.ema, "ema_updates": int(ema.n_averaged),
                 "ema_last_weight": ema.last_weight() if a.impl == "native" else 1.0 - a.ema}
                if ema is not None else {}),
+            **evals,
             "final_loss": final, "finite": True, "kernel_choices": _choices(), "steps_total": executed + a.steps, **({"tag": a.tag} if a.tag else {}),
         }), flush=True)
     env.destroy_process_group()

@@ -28,6 +28,7 @@ using at::Tensor;
 void bind_engine(py::module_& m);
 void bind_optim(py::module_& m);
 void bind_averaging(py::module_& m);
+void bind_eval(py::module_& m);
 void bind_math(py::module_& m);
 void bind_norm(py::module_& m);
 void bind_int8(py::module_& m);

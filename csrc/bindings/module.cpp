@@ -10,6 +10,7 @@ PYBIND11_MODULE(_C, m) {
   bind_engine(m);
   bind_optim(m);
   bind_averaging(m);
+  bind_eval(m);
   bind_math(m);
   bind_norm(m);
   bind_int8(m);

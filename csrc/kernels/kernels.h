@@ -352,6 +352,28 @@ hipError_t avg_update_multi(const AvgList& l, int src_dtype, const float* w, hip
 hipError_t avg_update_flat(float* a, const void* p, int src_dtype, uint16_t* shadow, uint16_t* copy, int64_t numel,
                            const float* w, hipStream_t s);
 
+// --------------------------------------------------------------------------
+// Evaluation metrics (csrc/kernels/eval_metrics.hip): cross-entropy and target rank per row in one
+// pass over the logits, and their fixed-order accumulation. Capturable as the averaging launches.
+constexpr int kEvalMaxK = 8;             // top-k thresholds per meter
+constexpr int kEvalCounters = 5;         // rows, valid, ignored, bad_target, nonfinite (then one per k)
+constexpr int kEvalRowsPerBlock = 4;     // rows of C <= kEvalWaveRowMaxC: one wave each
+constexpr int kEvalWaveRowMaxC = 2048;   // longer rows: one workgroup each
+struct EvalTopK {
+  int n;
+  int k[kEvalMaxK];  // strictly increasing, 1 <= k <= C
+};
+// logits: [B, C] f32 or bf16, rows `ld` elements apart (ld >= C), target int64[B]. row_loss[b] = lse - z_y,
+// rank[b] = #(z_c > z_y) + #(z_c == z_y, c < y); target == ignore_index: (0, -1); any other target outside
+// [0, C): (0, -2), the row is not read; z_y NaN: rank C. One row's results depend on its contents and C alone.
+hipError_t eval_rows(const void* logits, int dtype, int64_t ld, const int64_t* target, int B, int C,
+                     int64_t ignore_index, float* row_loss, int32_t* rank, hipStream_t s);
+// counters (int64[kEvalCounters + ks.n]) += rows, valid, ignored, bad_target, nonfinite, correct[k_i] (valid
+// rows of rank < k_i); loss_sum (float64[1]) += the finite losses of valid rows. One workgroup, no atomics:
+// the same inputs give the same bits.
+hipError_t eval_accumulate(const float* row_loss, const int32_t* rank, int B, const EvalTopK& ks, int64_t* counters,
+                           double* loss_sum, hipStream_t s);
+
 // dst[i] = src_i * scale over a list (bucket pack) or the reverse (unpack).
 struct CopyList {
   int n;

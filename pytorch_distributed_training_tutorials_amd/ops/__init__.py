@@ -7,5 +7,6 @@ from .linear import Linear, gemm, linear  # noqa: F401
 from .loss import CrossEntropyLoss, MSELoss, cross_entropy, mse_loss  # noqa: F401
 from .lr_scheduler import (ConstantLR, CosineAnnealingLR, ExponentialLR, LinearLR, MultiStepLR,  # noqa: F401
                            PolynomialLR, SequentialLR, StepLR)
+from .metrics import ClassificationMeter, classification_rows  # noqa: F401
 from .norm import BatchNorm2d, SyncBatchNorm  # noqa: F401
 from .optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD, layerwise_param_groups  # noqa: F401

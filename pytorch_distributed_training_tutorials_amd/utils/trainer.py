@@ -39,6 +39,8 @@ callable ``optimizer -> scheduler``) is stepped once per batch after
 ``model -> AveragedModel`` called once the model is on its device) takes one
 ``update_parameters`` per batch after the optimizer and the scheduler stepped, and is
 saved in snapshots; autograd engine only, as clipping.
+``evaluate(dataloader, model=...)`` scores the model or its averaged copy (ops/metrics.py:
+device-resident loss / top-k meter, one host read at the end); every engine.
 """
 from __future__ import annotations
 
@@ -432,3 +434,51 @@ class Trainer:
                 self._save_snapshot(epoch - 1)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
+
+    # ------------------------------------------------------------ evaluation
+    def evaluate(self, dataloader, *, model=None, topk=(1, 5), autocast_dtype=None) -> dict:
+        """Cross-entropy and top-k accuracy of ``model`` (default: the trained model; the
+        ``averaged_model`` is a valid argument) over ``dataloader``, whose batches are
+        ``(inputs, int64 class targets)``. The model runs in ``eval()`` mode under ``torch.no_grad()``
+        (and under ``torch.autocast(dtype=autocast_dtype)`` when given) and feeds an
+        ``ops.ClassificationMeter``; nothing is read on the host until the last batch is enqueued.
+        The counts are summed over the ranks of the trainer's communicator, every module's previous
+        ``training`` flag is restored, and rank 0 writes an ``event="eval"`` record to the metrics
+        sink. Returns ``{"loss", "top{k}"..., "count", "ignored", "nonfinite"}``.
+
+        Works on every engine: the fused and persistent engines' parameters are live views of the
+        engine's flat buffer, and the device is synchronised first so that a launch still running
+        has finished with them.
+
+        Samples are counted as the loader yields them. A ``DistributedSampler`` that pads the
+        dataset to a multiple of the world size repeats samples, and each repeat counts: for exact
+        figures give every rank a loader over its own disjoint shard."""
+        from ..ops.metrics import ClassificationMeter
+
+        model = self.model if model is None else model
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        meter = ClassificationMeter(topk, device=self.device)
+        modes = [(m, m.training) for m in model.modules()]
+        batches = 0
+        t0 = time.perf_counter()
+        model.eval()
+        try:
+            with torch.no_grad():
+                for xs, ys in dataloader:
+                    xs = xs.to(self.device, non_blocking=True)
+                    ys = ys.to(self.device, non_blocking=True)
+                    if autocast_dtype is None:
+                        out = model(xs)
+                    else:
+                        with torch.autocast(self.device.type, dtype=autocast_dtype):
+                            out = model(xs)
+                    meter.update(out, ys)
+                    batches += 1
+            result = meter.compute(self.comm)
+        finally:
+            for m, flag in modes:
+                m.training = flag
+        self.metrics.write(event="eval", batches=batches, seconds=time.perf_counter() - t0,
+                           model=type(model).__name__, **result)
+        return result
