@@ -16,7 +16,7 @@
 // grid (row blocks, channel tiles): threads of a block cover TC channel vectors
 // x RPI rows and walk the block's row range; partial sums are combined in LDS,
 // written per row block, and the LAST row block of each channel tile to finish
-// (atomic ticket; sc1 partial stores/loads, see last_block) reduces the partials
+// (atomic ticket; sc1 partial stores/loads, see handoff.h) reduces the partials
 // in fixed order (deterministic), computes the per-channel coefficients and
 // re-arms its ticket. So a BN forward is 2 launches (stats, apply) and a
 // backward 2 launches (reduce, apply).
@@ -37,11 +37,13 @@
 // The ReLU mask comes from the forward output y, or -- for BNs without a residual
 // -- is recomputed from x with the forward's own fmaf(x, scale, shift), sparing
 // one of the three reads in both backward passes.
-#include <cstdlib>
 #include <type_traits>
 
+#include "bn_finish.h"
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
+#include "vec16.h"
 
 namespace ptdt {
 namespace {
@@ -51,10 +53,6 @@ constexpr int kRed = 512;       // reduction kernels
 constexpr int kRedBlocks = 384; // ~1.5 reduction blocks per CU
 constexpr int kMaxGx = 256;     // row blocks per channel tile (bounds the last block's combine)
 
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
 // channel vectors per block row of a reduction (a tile of TC*V channels): 32 (whole 512-B rows
 // of a C = 256 bf16 tensor per 32 lanes) for tall tensors, where the wider tile measured up to
 // 13 % faster, 8 below (more row blocks to fill the chip; profiles/r3_bn_sweep.md).
@@ -89,44 +87,9 @@ int apply_block_cap() {
   return v;
 }
 
-template <typename T>
-struct VecIO {
-  static constexpr int V = 16 / sizeof(T);
-  __device__ __forceinline__ static void load(const T* p, float (&v)[V]) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    if constexpr (sizeof(T) == 4) {
-      v[0] = __uint_as_float(u.x); v[1] = __uint_as_float(u.y);
-      v[2] = __uint_as_float(u.z); v[3] = __uint_as_float(u.w);
-    } else {
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-      }
-    }
-  }
-  __device__ __forceinline__ static void store(T* p, const float (&v)[V]) {
-    uint4 u;
-    if constexpr (sizeof(T) == 4) {
-      u.x = __float_as_uint(v[0]); u.y = __float_as_uint(v[1]);
-      u.z = __float_as_uint(v[2]); u.w = __float_as_uint(v[3]);
-    } else {
-      uint32_t w[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-      u.x = w[0]; u.y = w[1]; u.z = w[2]; u.w = w[3];
-    }
-    *reinterpret_cast<uint4*>(p) = u;
-  }
-};
-
 // Row order of the reduction passes (PTDT_BN_INTERLEAVE=0: one contiguous slab per row block).
 int interleave_rows() {
-  static const int v = [] {
-    const char* e = getenv("PTDT_BN_INTERLEAVE");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
+  static const int v = env_int("PTDT_BN_INTERLEAVE", 1) != 0;
   return v;
 }
 
@@ -155,7 +118,7 @@ struct Geom {
 
 template <typename T>
 Geom geom(int64_t M, int C) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   Geom g;
   const int cv = C / V, mt = max_tc(M);
   g.TC = cv < mt ? cv : mt;
@@ -198,23 +161,6 @@ __device__ __forceinline__ void block_rows_sum(float (&acc)[NS][V], float* sh, i
   }
 }
 
-// Partials cross workgroups through sc1 (write-through, L1-bypassing) agent-scope relaxed stores and
-// loads; the ticket's returned value names the last arriver (MI355X_MICROARCH.md, hand-off table row
-// 1). The agent-scope release fence this replaced wrote back the XCD L2's dirty lines once per
-// workgroup -- with the backward's g tensor streaming out through those L2s, a per-block cost at the
-// tail of every reduction (profiles/r3_convbn.md shows the same fence at +110 us on a GEMM).
-typedef __attribute__((address_space(1))) float gfloat_t;
-// PTDT_BN_FENCE=1 (A/B measurements only): plain partial stores/loads behind the agent-scope
-// release (every block) and acquire (last block) fences this hand-off replaced.
-__device__ __forceinline__ void st_sc1(float* p, float v, bool fence = false) {
-  if (fence) *p = v;
-  else __hip_atomic_store((gfloat_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_sc1(const float* p, bool fence = false) {
-  if (fence) return *p;
-  return __hip_atomic_load((gfloat_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Last block of a channel tile: sum the gx row-block partials (two [gx][C] slabs) of the tile's
 // `width` channels with ALL threads. Thread (part, quad) adds rows part, part + P, ... of 4
 // consecutive channels (P = kRed / (width / 4) parts), kCombineRows rows x 2 slabs of two 8-B
@@ -228,13 +174,6 @@ constexpr int kCombineRows = 4;
 // is the size every combine needs, not a worst case (ADVICE r5 asked to size it per launch). It does
 // not cost occupancy: a CU holds 4 of these 512-thread blocks by waves (32), 128 KiB of LDS.
 constexpr size_t kCombineLds = (size_t)2 * kRed * 4 * sizeof(double);
-__device__ __forceinline__ void ld2_sc1(const float* p, float& x, float& y, bool fence) {
-  uint64_t u;
-  if (fence) u = *reinterpret_cast<const uint64_t*>(p);
-  else u = __hip_atomic_load(reinterpret_cast<const uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  x = __uint_as_float((uint32_t)u);
-  y = __uint_as_float((uint32_t)(u >> 32));
-}
 __device__ __forceinline__ void combine_partials(const float* ws, int gx, int C, int cbase, int width, float* sh,
                                                  double& s0, double& s1, bool fence) {
   const int nq = width >> 2;
@@ -288,44 +227,6 @@ __device__ __forceinline__ void combine_partials(const float* ws, int gx, int C,
   }
 }
 
-// Atomic ticket: true in exactly one block per channel tile (the last to arrive), after every
-// block's sc1 partial stores have landed (each wave drains its own, then the barrier), told by the
-// value the relaxed agent-scope add returns. The flag travels through the kernel's one LDS array.
-//
-// Memory-model note (ISA-level, gfx950): the HIP/LLVM model gives relaxed atomics no
-// happens-before, so correctness rests on the hardware, not the language: (1) the partials are
-// written with sc1 stores (write-through to the coherent level) and each wave waits vmcnt(0)
-// before the barrier, so they are globally visible before the ticket add issues; (2) the last
-// block reads them with sc1 loads, which miss the non-coherent caches. The compiler cannot move
-// those loads above the ticket: __syncthreads() after the flag write is a workgroup-scope
-// release/acquire fence pair, and the explicit signal fence below pins the order in the IR too.
-// tests/test_norm.py compares this hand-off with the fence-based one (PTDT_BN_FENCE=1) bit for bit
-// on many-block shapes.
-__device__ __forceinline__ bool last_block(int* ticket, int* sh_flag, bool fence) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (fence) {  // A/B: the replaced form (write-back of this XCD's L2 before the ticket)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const int prev = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == (int)gridDim.x - 1;
-    if (last && fence) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *sh_flag = last;
-  }
-  __syncthreads();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);  // no load of the partials is hoisted above this point
-  return *sh_flag != 0;
-}
-
-__device__ __forceinline__ void rearm(int* ticket) {
-  __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Cross-rank statistics (SyncBatchNorm, ops/norm.py). SYNC / RAW instances of the two reduction
 // kernels stop before the local row count finalises anything: the last block writes this rank's
 // float64 record instead, the ranks exchange the records, and bn_sync_merge_kernel /
@@ -353,7 +254,7 @@ template <typename T, bool SYNC = false>
 __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x, int64_t M, int C, int TC, int RPI,
                                                         int64_t rows_per_block, int il, float* ws, int* tickets,
                                                         std::conditional_t<SYNC, BnSyncParams, BnParams> p) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   constexpr int U = 8;  // rows in flight per thread
   extern __shared__ float sh[];  // 2 x RPI x TC*V reduction slots, then the last-block flag
   int* flag = reinterpret_cast<int*>(sh + 2 * kRed * V);
@@ -375,16 +276,16 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
   for (int v = 0; v < V; ++v) acc[0][v] = acc[1][v] = 0.f;
   if (active) {
     float K[V], K1[V], K2[V];  // pivot (same for every block): pivot_of(), a vector at a time
-    VecIO<T>::load(x + c0, K);
-    VecIO<T>::load(x + (M / 2) * C + c0, K1);
-    VecIO<T>::load(x + (M - 1) * C + c0, K2);
+    Vec16<T>::load(x + c0, K);
+    Vec16<T>::load(x + (M / 2) * C + c0, K1);
+    Vec16<T>::load(x + (M - 1) * C + c0, K2);
 #pragma unroll
     for (int v = 0; v < V; ++v) K[v] = median3(K[v], K1[v], K2[v]);
     int64_t r = rb + rr;
     for (; r + (U - 1) * rs < re; r += U * rs) {  // U independent 16-B loads in flight
       float a[U][V];
 #pragma unroll
-      for (int u = 0; u < U; ++u) VecIO<T>::load(x + row(r + u * rs) * C + c0, a[u]);
+      for (int u = 0; u < U; ++u) Vec16<T>::load(x + row(r + u * rs) * C + c0, a[u]);
       // each batch of U rows is summed on its own and then added: a running float sum of every
       // row stagnates on bf16 data (the addends sit on a coarse grid and tie after tie rounds to
       // even, i.e. down), which biased the variance low by up to 2e-6 of itself on tall tensors
@@ -407,7 +308,7 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
     }
     for (; r < re; r += rs) {
       float a[V];
-      VecIO<T>::load(x + row(r) * C + c0, a);
+      Vec16<T>::load(x + row(r) * C + c0, a);
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         const float d = a[v] - K[v];
@@ -420,13 +321,14 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
   block_rows_sum<V, 2>(acc, sh, TC, RPI, part);
   const int width = TC * V;
   const int c = blockIdx.y * width + tid;
+  const int gx = (int)gridDim.x;  // row blocks: the ticket's count
   if (tid < width && c < C) {
     st_sc1(ws + (int64_t)blockIdx.x * C + c, part[0], (p.fence_handoff != 0));
-    st_sc1(ws + ((int64_t)gridDim.x + blockIdx.x) * C + c, part[1], (p.fence_handoff != 0));
+    st_sc1(ws + ((int64_t)gx + blockIdx.x) * C + c, part[1], (p.fence_handoff != 0));
   }
-  if (!last_block(tickets + blockIdx.y, flag, (p.fence_handoff != 0))) return;
+  if (!last_arrival(tickets + blockIdx.y, gx, flag, (p.fence_handoff != 0))) return;
   double s, q;
-  combine_partials(ws, (int)gridDim.x, C, blockIdx.y * width, width, sh, s, q, (p.fence_handoff != 0));
+  combine_partials(ws, gx, C, blockIdx.y * width, width, sh, s, q, (p.fence_handoff != 0));
   if constexpr (SYNC) {  // this rank's record; invstd and the running statistics wait for the merge
     if (tid < width && c < C) {
       double m2 = q - s * s / (double)M;
@@ -434,10 +336,7 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
       p.rec[c] = (double)pivot_of<T>(x, M, C, c) + s / (double)M;
       p.rec[C + c] = m2;
     }
-    if (tid == 0) {
-      rearm(tickets + blockIdx.y);
-      if (blockIdx.y == 0) p.rec[2 * C] = (double)M;
-    }
+    if (tid == 0 && blockIdx.y == 0) p.rec[2 * C] = (double)M;
     return;
   }
   if (tid < width && c < C) {
@@ -445,23 +344,9 @@ __global__ void __launch_bounds__(kRed) bn_stats_kernel(const T* __restrict__ x,
     const double ms = s / (double)M;
     double var = q / (double)M - ms * ms;
     if (var < 0.0) var = 0.0;
-    const double mean = Kc + ms;
-    const float invstd = (float)(1.0 / sqrt(var + (double)p.eps));
-    const float w = p.weight ? p.weight[c] : 1.f, b = p.bias ? p.bias[c] : 0.f;
-    p.mean[c] = (float)mean;
-    p.invstd[c] = invstd;
-    p.scale[c] = w * invstd;
-    p.shift[c] = b - (float)mean * w * invstd;
-    if (p.running_mean) {
-      const double unbiased = M > 1 ? var * (double)M / (double)(M - 1) : var;
-      p.running_mean[c] = (float)((1.0 - p.momentum) * p.running_mean[c] + p.momentum * mean);
-      p.running_var[c] = (float)((1.0 - p.momentum) * p.running_var[c] + p.momentum * unbiased);
-    }
+    bn_finish_channel(p, c, Kc + ms, var, M > 1 ? var * (double)M / (double)(M - 1) : var);
   }
-  if (tid == 0) {
-    rearm(tickets + blockIdx.y);  // for the next launch (stream order)
-    if (blockIdx.y == 0 && p.num_batches_tracked) *p.num_batches_tracked += 1;
-  }
+  if (tid == 0 && blockIdx.y == 0 && p.num_batches_tracked) *p.num_batches_tracked += 1;
 }
 
 // Merge of the W gathered records ([W, 2 C + 1], rank-major) into the [4, C] statistics the apply
@@ -492,17 +377,7 @@ __global__ void __launch_bounds__(kThreads) bn_sync_merge_kernel(const double* _
     }
   }
   const double var = n > 0.0 ? m2 / n : 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)p.eps));
-  const float w = p.weight ? p.weight[c] : 1.f, b = p.bias ? p.bias[c] : 0.f;
-  p.mean[c] = (float)mean;
-  p.invstd[c] = invstd;
-  p.scale[c] = w * invstd;
-  p.shift[c] = b - (float)mean * w * invstd;
-  if (p.running_mean) {
-    const double unbiased = n > 1.0 ? m2 / (n - 1.0) : var;
-    p.running_mean[c] = (float)((1.0 - p.momentum) * p.running_mean[c] + p.momentum * mean);
-    p.running_var[c] = (float)((1.0 - p.momentum) * p.running_var[c] + p.momentum * unbiased);
-  }
+  bn_finish_channel(p, c, mean, var, n > 1.0 ? m2 / (n - 1.0) : var);
   if (c == 0) {
     *count = n;
     if (p.num_batches_tracked) *p.num_batches_tracked += 1;
@@ -516,14 +391,7 @@ __global__ void __launch_bounds__(kThreads) bn_sync_coef_kernel(const double* __
                                                                 BnBwdParams p) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double N = *count;
-  const double sdy = sums[c], sdx = sums[C + c];
-  const double invstd = p.invstd[c], mean = p.mean[c];
-  const double w = p.weight ? p.weight[c] : 1.0;
-  const double k = w * invstd, s1 = sdy / N, s2 = invstd * invstd * sdx / N;
-  p.coef_a[c] = (float)k;
-  p.coef_b[c] = (float)(-k * s2);
-  p.coef_c[c] = (float)(k * s2 * mean - k * s1);
+  bn_bwd_coef_channel(p, c, sums[c], sums[C + c], *count);
 }
 
 // MASKOUT: also write the ReLU mask, one byte per V-vector (bit v: y > 0), for a backward that
@@ -534,7 +402,7 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const T* __restrict_
                                                             T* __restrict__ y, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, int64_t nvec, int C,
                                                             int rev, uint8_t* __restrict__ mask) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   extern __shared__ float sh[];  // scale[C], shift[C]
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     sh[c] = scale[c];
@@ -550,8 +418,8 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const T* __restrict_
     for (int u = 0; u < AU; ++u) {
       const int64_t i = vid(i0 + u * stride);
       if (i0 + u * stride < nvec) {
-        VecIO<T>::load(x + i * V, a[u]);
-        if constexpr (RES) VecIO<T>::load(res + i * V, rv[u]);
+        Vec16<T>::load(x + i * V, a[u]);
+        if constexpr (RES) Vec16<T>::load(res + i * V, rv[u]);
       }
     }
 #pragma unroll
@@ -568,7 +436,7 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const T* __restrict_
         if constexpr (MASKOUT) bits |= (o > 0.f ? 1u : 0u) << v;
         a[u][v] = o;
       }
-      VecIO<T>::store(y + i * V, a[u]);
+      Vec16<T>::store(y + i * V, a[u]);
       if constexpr (MASKOUT) mask[i] = (uint8_t)bits;
     }
   }
@@ -585,13 +453,6 @@ __device__ __forceinline__ float masked_dy(float g, float x, float y, float sc, 
   return g;
 }
 
-// T-rounded value (what a T tensor holds): identity for f32
-template <typename T>
-__device__ __forceinline__ float round_to(float v) {
-  if constexpr (sizeof(T) == 4) return v;
-  return bf16_to_f32(f32_to_bf16(v));
-}
-
 // GOUT: the masked gradient g = mask (dy + dy2), rounded to T, is also written (to gout): it IS
 // the residual gradient, and the apply pass then reads g and x only (bn_bwd_apply_g_kernel)
 // instead of dy, dy2, x and the mask. The sums use the rounded g, so both passes agree.
@@ -605,7 +466,7 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
                                                              int RPI, int64_t rows_per_block, int il, float* ws,
                                                              int* tickets,
                                                              std::conditional_t<RAW, BnSyncBwdParams, BnBwdParams> p) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   constexpr int U = 4;  // rows in flight per thread (x 2-3 loads each)
   extern __shared__ float sh[];
   int* flag = reinterpret_cast<int*>(sh + 2 * kRed * V);
@@ -634,7 +495,7 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
     // ReLU mask operand o[v] (0 / 1 bits for MASK 3, y for MASK 1)
     auto load_mask = [&](int64_t row, int64_t off, float (&o)[V]) {
       if constexpr (MASK == 1) {
-        VecIO<T>::load(y + off, o);
+        Vec16<T>::load(y + off, o);
       } else if constexpr (MASK == 3) {
         const unsigned b = mk[row * cv + c0 / V];
 #pragma unroll
@@ -650,16 +511,16 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
         acc[0][v] += gg;
         acc[1][v] = fmaf(gg, a[v] - mu[v], acc[1][v]);
       }
-      if constexpr (GOUT) VecIO<T>::store(gout + off, g);
+      if constexpr (GOUT) Vec16<T>::store(gout + off, g);
     };
     for (; r + (U - 1) * rs < re; r += U * rs) {
       float g[U][V], a[U][V], o[U][V], g2[ADD2 ? U : 1][V];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t off = row(r + u * rs) * C + c0;
-        VecIO<T>::load(dy + off, g[u]);
-        if constexpr (ADD2) VecIO<T>::load(dy2 + off, g2[u]);
-        VecIO<T>::load(x + off, a[u]);
+        Vec16<T>::load(dy + off, g[u]);
+        if constexpr (ADD2) Vec16<T>::load(dy2 + off, g2[u]);
+        Vec16<T>::load(x + off, a[u]);
         load_mask(row(r + u * rs), off, o[u]);
       }
       if constexpr (ADD2) {
@@ -674,14 +535,14 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
     for (; r < re; r += rs) {
       float g[V], a[V], o[V];
       const int64_t off = row(r) * C + c0;
-      VecIO<T>::load(dy + off, g);
+      Vec16<T>::load(dy + off, g);
       if constexpr (ADD2) {
         float g2[V];
-        VecIO<T>::load(dy2 + off, g2);
+        Vec16<T>::load(dy2 + off, g2);
 #pragma unroll
         for (int v = 0; v < V; ++v) g[v] += g2[v];
       }
-      VecIO<T>::load(x + off, a);
+      Vec16<T>::load(x + off, a);
       load_mask(row(r), off, o);
       finish(g, a, o, off);
     }
@@ -690,34 +551,21 @@ __global__ void __launch_bounds__(kRed) bn_bwd_reduce_kernel(const T* __restrict
   block_rows_sum<V, 2>(acc, sh, TC, RPI, part);
   const int width = TC * V;
   const int c = blockIdx.y * width + tid;
+  const int gx = (int)gridDim.x;  // row blocks: the ticket's count
   if (tid < width && c < C) {
     st_sc1(ws + (int64_t)blockIdx.x * C + c, part[0], (p.fence_handoff != 0));
-    st_sc1(ws + ((int64_t)gridDim.x + blockIdx.x) * C + c, part[1], (p.fence_handoff != 0));
+    st_sc1(ws + ((int64_t)gx + blockIdx.x) * C + c, part[1], (p.fence_handoff != 0));
   }
-  if (!last_block(tickets + blockIdx.y, flag, (p.fence_handoff != 0))) return;
+  if (!last_arrival(tickets + blockIdx.y, gx, flag, (p.fence_handoff != 0))) return;
   double sdy, sdx;
-  combine_partials(ws, (int)gridDim.x, C, blockIdx.y * width, width, sh, sdy, sdx, (p.fence_handoff != 0));
-  if constexpr (RAW) {
+  combine_partials(ws, gx, C, blockIdx.y * width, width, sh, sdy, sdx, (p.fence_handoff != 0));
+  if constexpr (RAW) {  // this rank's sums for the all-reduce; the coefficients wait for bn_sync_coef_kernel
     if (tid < width && c < C) {
       p.sums[c] = sdy;
       p.sums[C + c] = sdx;
-      if (p.dweight) p.dweight[c] = (float)(sdx * (double)p.invstd[c]);
-      if (p.dbias) p.dbias[c] = (float)sdy;
     }
-    if (tid == 0) rearm(tickets + blockIdx.y);
-    return;
   }
-  if (tid < width && c < C) {
-    const double invstd = p.invstd[c], mean = p.mean[c];
-    const double w = p.weight ? p.weight[c] : 1.0;
-    if (p.dweight) p.dweight[c] = (float)(sdx * invstd);
-    if (p.dbias) p.dbias[c] = (float)sdy;
-    const double k = w * invstd, s1 = sdy / (double)M, s2 = invstd * invstd * sdx / (double)M;
-    p.coef_a[c] = (float)k;
-    p.coef_b[c] = (float)(-k * s2);
-    p.coef_c[c] = (float)(k * s2 * mean - k * s1);
-  }
-  if (tid == 0) rearm(tickets + blockIdx.y);
+  if (tid < width && c < C) bn_bwd_finish_channel(p, c, sdy, sdx, (double)M, !RAW);
 }
 
 // dx = A g + B x + C from the reduce pass's materialised g (GOUT): 2 reads + 1 write
@@ -725,7 +573,7 @@ template <typename T, int AU = 1>
 __global__ void __launch_bounds__(kThreads) bn_bwd_apply_g_kernel(const T* __restrict__ g, const T* __restrict__ x,
                                                                   T* __restrict__ dx, BnBwdParams p, int64_t nvec,
                                                                   int C, int rev) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   extern __shared__ float sh[];  // A[C], B[C], C[C]
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     sh[c] = p.coef_a[c];
@@ -742,8 +590,8 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_g_kernel(const T* __res
     for (int u = 0; u < AU; ++u) {
       const int64_t i = vid(i0 + u * stride);
       if (i0 + u * stride < nvec) {
-        VecIO<T>::load(g + i * V, gg[u]);
-        VecIO<T>::load(x + i * V, a[u]);
+        Vec16<T>::load(g + i * V, gg[u]);
+        Vec16<T>::load(x + i * V, a[u]);
       }
     }
 #pragma unroll
@@ -754,7 +602,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_g_kernel(const T* __res
 #pragma unroll
       for (int v = 0; v < V; ++v)
         a[u][v] = fmaf(sh[c0 + v], gg[u][v], fmaf(sh[C + c0 + v], a[u][v], sh[2 * C + c0 + v]));
-      VecIO<T>::store(dx + i * V, a[u]);
+      Vec16<T>::store(dx + i * V, a[u]);
     }
   }
 }
@@ -765,7 +613,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const T* __restr
                                                                 const T* __restrict__ y, T* __restrict__ dx,
                                                                 T* __restrict__ dres, BnBwdParams p, int64_t nvec,
                                                                 int C, int rev) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   extern __shared__ float sh[];  // A[C], B[C], C[C] (+ scale[C], shift[C] for MASK 2)
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     sh[c] = p.coef_a[c];
@@ -786,10 +634,10 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const T* __restr
     for (int u = 0; u < AU; ++u) {
       const int64_t i = vid(i0 + u * stride);
       if (i0 + u * stride < nvec) {
-        VecIO<T>::load(dy + i * V, g[u]);
-        if constexpr (ADD2) VecIO<T>::load(dy2 + i * V, g2[u]);
-        VecIO<T>::load(x + i * V, a[u]);
-        if constexpr (MASK == 1) VecIO<T>::load(y + i * V, o[u]);
+        Vec16<T>::load(dy + i * V, g[u]);
+        if constexpr (ADD2) Vec16<T>::load(dy2 + i * V, g2[u]);
+        Vec16<T>::load(x + i * V, a[u]);
+        if constexpr (MASK == 1) Vec16<T>::load(y + i * V, o[u]);
       }
     }
 #pragma unroll
@@ -806,8 +654,8 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const T* __restr
         g[u][v] = gv;
         a[u][v] = fmaf(sh[c0 + v], gv, fmaf(sh[C + c0 + v], a[u][v], sh[2 * C + c0 + v]));
       }
-      VecIO<T>::store(dx + i * V, a[u]);
-      if constexpr (RES) VecIO<T>::store(dres + i * V, g[u]);
+      Vec16<T>::store(dx + i * V, a[u]);
+      if constexpr (RES) Vec16<T>::store(dres + i * V, g[u]);
     }
   }
 }
@@ -816,7 +664,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const T* __restr
 // and the combine's part sums (kCombineLds) share one array
 template <typename T>
 size_t red_lds() {
-  const size_t rows = (size_t)2 * kRed * VecIO<T>::V * sizeof(float) + 16;
+  const size_t rows = (size_t)2 * kRed * Vec16<T>::N * sizeof(float) + 16;
   return rows > kCombineLds ? rows : kCombineLds;
 }
 
@@ -865,7 +713,7 @@ hipError_t with_au(F&& f) {
 
 template <typename T>
 hipError_t fwd_impl(const BnFwdArgs& a, hipStream_t s) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   if (a.C % V != 0) return hipErrorInvalidValue;
   const Geom g = geom<T>(a.M, a.C);
   const size_t sh_red = red_lds<T>();
@@ -901,7 +749,7 @@ hipError_t fwd_impl(const BnFwdArgs& a, hipStream_t s) {
 template <typename T>
 hipError_t apply_impl(const void* x, const void* res, void* y, const float* scale, const float* shift, int64_t M,
                       int C, int relu, hipStream_t s) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   if (C % V != 0) return hipErrorInvalidValue;
   const int64_t nvec = M * C / V;
   const size_t sh_ap = (size_t)2 * C * sizeof(float);
@@ -923,7 +771,7 @@ hipError_t apply_impl(const void* x, const void* res, void* y, const float* scal
 
 template <typename T, int MASK, bool ADD2>
 hipError_t bwd_launch(const BnBwdArgs& a, const Geom& g, hipStream_t s) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   const size_t sh_red = red_lds<T>();
   const T* dy = static_cast<const T*>(a.dy);
   const T* dy2 = static_cast<const T*>(a.dy2);
@@ -972,7 +820,7 @@ hipError_t bwd_launch2(const BnBwdArgs& a, const Geom& g, hipStream_t s) {
 
 template <typename T>
 hipError_t bwd_impl(const BnBwdArgs& a, hipStream_t s) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   if (a.C % V != 0) return hipErrorInvalidValue;
   const Geom g = geom<T>(a.M, a.C);
   if (!a.relu) return bwd_launch2<T, 0>(a, g, s);
@@ -989,7 +837,7 @@ hipError_t bwd_impl(const BnBwdArgs& a, hipStream_t s) {
 template <typename T>
 hipError_t sync_stats_impl(const void* x, int64_t M, int C, float* ws, int* tickets, double* rec, int fence,
                            hipStream_t s) {
-  if (C % VecIO<T>::V != 0) return hipErrorInvalidValue;
+  if (C % Vec16<T>::N != 0) return hipErrorInvalidValue;
   const Geom g = geom<T>(M, C);
   BnSyncParams p{};
   p.rec = rec;
@@ -1015,7 +863,7 @@ hipError_t sync_reduce_launch(const BnBwdArgs& a, double* sums, hipStream_t s) {
 
 template <typename T>
 hipError_t sync_reduce_impl(const BnBwdArgs& a, double* sums, hipStream_t s) {
-  if (a.C % VecIO<T>::V != 0 || a.dres == nullptr) return hipErrorInvalidValue;
+  if (a.C % Vec16<T>::N != 0 || a.dres == nullptr) return hipErrorInvalidValue;
   const bool add2 = a.dy2 != nullptr;
   if (!a.relu) return add2 ? sync_reduce_launch<T, 0, true>(a, sums, s) : sync_reduce_launch<T, 0, false>(a, sums, s);
   if (a.mask != nullptr)
@@ -1026,7 +874,7 @@ hipError_t sync_reduce_impl(const BnBwdArgs& a, double* sums, hipStream_t s) {
 
 template <typename T>
 hipError_t apply_g_impl(const void* g, const void* x, void* dx, const float* coef, int64_t M, int C, hipStream_t s) {
-  constexpr int V = VecIO<T>::V;
+  constexpr int V = Vec16<T>::N;
   if (C % V != 0) return hipErrorInvalidValue;
   const int64_t nvec = M * C / V;
   BnBwdParams p{};

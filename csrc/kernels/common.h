@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define PTDT_WAVE 64
 
@@ -32,6 +33,12 @@ __device__ __forceinline__ T PTDT_GLOBAL* gptr_w(T* p) {
 }
 
 __host__ __device__ __forceinline__ int al4(int n) { return (n + 3) & ~3; }
+
+// integer environment knob (host): unset or empty -> dflt
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return (e && e[0]) ? atoi(e) : dflt;
+}
 
 // ---------------------------------------------------------------- bf16 <-> f32
 // bf16 is stored as raw uint16_t in every kernel signature (no vendor types in

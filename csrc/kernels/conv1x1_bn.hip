@@ -22,8 +22,10 @@
 //   * statistics accumulate per lane in registers over the whole launch (its rows, its N/4
 //     channels), are reduced once at the end (DPP within the 16 lanes of a row, LDS across
 //     waves) into one [2, N] partial per workgroup, and merged by the last workgroup of each
-//     group / the last group (sc1 stores and loads + ticket, as gemm_bn_stats).
+//     group / the last group (sc1 stores and loads + ticket, handoff.h).
+#include "bn_finish.h"
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace ptdt {
@@ -35,30 +37,6 @@ typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
-typedef __attribute__((address_space(1))) float gfloat;
-
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-  __hip_atomic_store((gfloat*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load((gfloat*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool last_arrival(int* ticket, int count, int* sh_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sc1 partial stores have landed
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int prev = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == count - 1;
-    if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *sh_flag = last;
-  }
-  __syncthreads();
-  // relaxed atomics carry no happens-before in the HIP model: visibility rests on the sc1 stores /
-  // loads (see batchnorm.hip last_block); this fence keeps the partial loads below the ticket in the IR
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  return *sh_flag != 0;
-}
 
 template <int N>
 __device__ __forceinline__ void vm_wait() {
@@ -334,27 +312,12 @@ __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uin
     double var = b / Md - ms * ms;
     if (var < 0.0) var = 0.0;
     const double mean = (bp.running_mean ? (double)bp.running_mean[c] : 0.0) + ms;
-    const float invstd = (float)(1.0 / sqrt(var + (double)bp.eps));
-    const float w = bp.weight ? bp.weight[c] : 1.f, bb = bp.bias ? bp.bias[c] : 0.f;
-    bp.mean[c] = (float)mean;
-    bp.invstd[c] = invstd;
-    bp.scale[c] = w * invstd;
-    bp.shift[c] = bb - (float)mean * w * invstd;
-    if (bp.running_mean) {
-      const double unbiased = M > 1 ? var * Md / (Md - 1.0) : var;
-      bp.running_mean[c] = (float)((1.0 - bp.momentum) * bp.running_mean[c] + bp.momentum * mean);
-      bp.running_var[c] = (float)((1.0 - bp.momentum) * bp.running_var[c] + bp.momentum * unbiased);
-    }
+    bn_finish_channel(bp, c, mean, var, M > 1 ? var * Md / (Md - 1.0) : var);
   }
   if (tid == 0 && slab == 0 && bp.num_batches_tracked) *bp.num_batches_tracked += 1;
 }
 
 constexpr int kCus = 256;
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
 
 int stream_group(int G) {
   int g = 1;

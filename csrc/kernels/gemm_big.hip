@@ -36,8 +36,11 @@
 //     fragment reads frees the buffer for tile k+2.
 //   * edges: rows/cols past M/N read a clamped (valid) row and are not stored;
 //     K must be a multiple of 64 (host checks), bases 16-B aligned.
+#include "bn_finish.h"
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
+#include "vec16.h"
 
 namespace ptdt {
 namespace {
@@ -388,15 +391,13 @@ __global__ void __launch_bounds__(T::NT) gemm_bf16_lds_kernel(BigGemmArgs g, int
 //      about the wave's own column mean (two passes over registers, lanes combined with
 //      shuffles), written as one partial (row-disjoint, no atomics) per wave row;
 //   2. groups of G row tiles per column tile: the last workgroup of a group to finish (atomic
-//      ticket; partials handed over with sc1 stores/loads, see last_arrival) merges the group's partials in
+//      ticket; partials handed over with sc1 stores/loads, handoff.h) merges the group's partials in
 //      fixed order (Chan et al.'s pairwise update, in double) into one group partial;
 //   3. the last group of a column tile merges the group partials and writes mean, invstd,
 //      scale = w*invstd, shift = b - mean*scale (the [4, C] layout batchnorm.hip's backward
 //      reads), updates running_mean / running_var (unbiased) and num_batches_tracked.
 // Deterministic (fixed merge order whatever the arrival order) and robust for |mean| >> std
 // (centred partials). Tickets are re-armed by their last arriver for the next launch.
-__device__ __forceinline__ float bf16_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
-
 // (n, S, Q) <- (n, S, Q) merged with (np, Sp, Qp): S = sum, Q = sum of squares about the mean
 __device__ __forceinline__ void chan_merge(double& n, double& S, double& Q, double np, double Sp, double Qp) {
   if (np <= 0.0) return;
@@ -408,39 +409,6 @@ __device__ __forceinline__ void chan_merge(double& n, double& S, double& Q, doub
   Q += Qp + d * d * n * np / (n + np);
   S += Sp;
   n += np;
-}
-
-// Cross-workgroup hand-off of the statistics partials without L2 write-backs: every partial is
-// stored and loaded with sc1 (write-through / L1-bypassing agent-scope relaxed atomics), every
-// storing wave drains its stores (vmcnt(0)) before the workgroup barrier, then one lane adds to the
-// ticket and the add's returned value names the last arriver (MI355X_MICROARCH.md "Hand-offs
-// measured with sc1 loads", first row). An agent-scope release fence here would write back the
-// XCD L2's dirty lines -- the freshly stored output tiles -- once per workgroup: +110 us on a
-// 401408 x 256 conv (profiles/r3_convbn.md).
-typedef __attribute__((address_space(1))) float gfloat;
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-  __hip_atomic_store((gfloat*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load((gfloat*)p, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// true in exactly one workgroup per ticket (the count-th arriver); re-arms the ticket
-__device__ __forceinline__ bool last_arrival(int* ticket, int count, int* sh_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sc1 partial stores have landed
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int prev = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == count - 1;
-    if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *sh_flag = last;
-  }
-  __syncthreads();
-  // relaxed atomics carry no happens-before in the HIP model: visibility rests on the sc1 stores /
-  // loads (see batchnorm.hip last_block); this fence keeps the partial loads below the ticket in the IR
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  return *sh_flag != 0;
 }
 
 // Merge partials [p0, p1) (row counts from rows_of(p)) of this tile's BN columns; the NT/BN thread
@@ -501,7 +469,7 @@ __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, Gem
     for (int i = 0; i < T::FI; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (wrow0 + i * 16 + 4 * fq + r < g.M) a += bf16_round(acc[i][j][r]);
+        if (wrow0 + i * 16 + 4 * fq + r < g.M) a += round_to<uint16_t>(acc[i][j][r]);
     a += __shfl_xor(a, 16);
     a += __shfl_xor(a, 32);
     s[j] = a;
@@ -516,7 +484,7 @@ __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, Gem
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (wrow0 + i * 16 + 4 * fq + r < g.M) {
-          const float d = bf16_round(acc[i][j][r]) - mu;
+          const float d = round_to<uint16_t>(acc[i][j][r]) - mu;
           a = fmaf(d, d, a);
         }
     a += __shfl_xor(a, 16);
@@ -570,21 +538,9 @@ __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, Gem
   merge_range<T>(gS, gQ, N, n0, 0, ng, group_rows, sh, n, S, Q);
   const int c = n0 + tid;
   if (tid < T::BN && c < N) {
-    const BnParams& p = e.p;
     const double Md = (double)g.M;
-    const double mean = S / Md;
     const double var = Q / Md > 0.0 ? Q / Md : 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)p.eps));
-    const float w = p.weight ? p.weight[c] : 1.f, b = p.bias ? p.bias[c] : 0.f;
-    p.mean[c] = (float)mean;
-    p.invstd[c] = invstd;
-    p.scale[c] = w * invstd;
-    p.shift[c] = b - (float)mean * w * invstd;
-    if (p.running_mean) {
-      const double unbiased = g.M > 1 ? var * Md / (Md - 1.0) : var;
-      p.running_mean[c] = (float)((1.0 - p.momentum) * p.running_mean[c] + p.momentum * mean);
-      p.running_var[c] = (float)((1.0 - p.momentum) * p.running_var[c] + p.momentum * unbiased);
-    }
+    bn_finish_channel(e.p, c, S / Md, var, g.M > 1 ? var * Md / (Md - 1.0) : var);
   }
   if (tid == 0 && bn == 0 && e.p.num_batches_tracked) *e.p.num_batches_tracked += 1;
 }

@@ -14,55 +14,21 @@
 // first in-range tap in row-major window order, as in torch.
 #include "common.h"
 #include "kernels.h"
+#include "vec16.h"
 
 namespace ptdt {
 namespace {
 
 constexpr int kThreads = 256;
 
-template <typename T>
-struct V16 {
-  static constexpr int V = 16 / sizeof(T);
-  __device__ __forceinline__ static void load(const T* p, float (&v)[V]) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = __uint_as_float(w[i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-      }
-    }
-  }
-  __device__ __forceinline__ static void store(T* p, const float (&v)[V]) {
-    uint32_t w[4];
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = __float_as_uint(v[i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f32_to_bf16(v[2 * i]) | ((uint32_t)f32_to_bf16(v[2 * i + 1]) << 16);
-    }
-    *reinterpret_cast<uint4*>(p) = uint4{w[0], w[1], w[2], w[3]};
-  }
-};
-
 // AFF: the BatchNorm apply (+ReLU) of the pool's input done on load (PoolArgs.scale/shift/relu), with
 // the same fmaf and rounding as batchnorm.hip's apply pass: output and argmax are bit-identical to
 // BN-then-pool, without writing and re-reading the normalised activation.
-template <typename T>
-__device__ __forceinline__ float round_to(float v) {
-  if constexpr (sizeof(T) == 4) return v;
-  else return __uint_as_float((uint32_t)f32_to_bf16(v) << 16);
-}
-
+// (round_to<T>, vec16.h, is what both files store).
 template <typename T, bool AFF>
 __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                                uint8_t* __restrict__ arg, PoolArgs a) {
-  constexpr int V = V16<T>::V;
+  constexpr int V = Vec16<T>::N;
   const int cv = a.C / V;
   const int64_t total = (int64_t)a.N * a.Ho * a.Wo * cv;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -96,7 +62,7 @@ __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(const T* __restri
         const int w = w0 + dx;
         if (w < 0 || w >= a.W) continue;
         float v_[V];
-        V16<T>::load(x + (((int64_t)n * a.H + h) * a.W + w) * a.C + c0, v_);
+        Vec16<T>::load(x + (((int64_t)n * a.H + h) * a.W + w) * a.C + c0, v_);
         if constexpr (AFF) {
 #pragma unroll
           for (int v = 0; v < V; ++v) {
@@ -118,7 +84,7 @@ __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(const T* __restri
       }
     }
     const int64_t o = (((int64_t)n * a.Ho + ho) * a.Wo + wo) * a.C + c0;
-    V16<T>::store(y + o, best);
+    Vec16<T>::store(y + o, best);
     if constexpr (V == 8) {
       uint2 packed;
       packed.x = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
@@ -134,7 +100,7 @@ template <typename T>
 __global__ void __launch_bounds__(kThreads) maxpool_bwd_kernel(const T* __restrict__ gy,
                                                                const uint8_t* __restrict__ arg, T* __restrict__ gx,
                                                                PoolArgs a) {
-  constexpr int V = V16<T>::V;
+  constexpr int V = Vec16<T>::N;
   const int cv = a.C / V;
   const int64_t total = (int64_t)a.N * a.H * a.W * cv;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -168,13 +134,13 @@ __global__ void __launch_bounds__(kThreads) maxpool_bwd_kernel(const T* __restri
           b[1] = 0;
         }
         float g[V];
-        V16<T>::load(gy + o, g);
+        Vec16<T>::load(gy + o, g);
 #pragma unroll
         for (int v = 0; v < V; ++v)
           if (((b[v >> 2] >> (8 * (v & 3))) & 0xffu) == k) acc[v] += g[v];
       }
     }
-    V16<T>::store(gx + (((int64_t)n * a.H + h) * a.W + w) * a.C + c0, acc);
+    Vec16<T>::store(gx + (((int64_t)n * a.H + h) * a.W + w) * a.C + c0, acc);
   }
 }
 
