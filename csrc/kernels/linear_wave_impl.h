@@ -966,6 +966,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_kernel(FusedMlpArgs a, P
 struct F2 {
   float a, b;
 };
+// Packed fp32 (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth of FMAs per issue slot).
+typedef float f2v __attribute__((ext_vector_type(2)));
 // permlane16_swap(A, B): A' = rows [A0, B0, A2, B2], B' = rows [A1, B1, A3, B3]
 __device__ __forceinline__ F2 pl16(float a, float b) {
   auto p = __builtin_amdgcn_permlane16_swap(__float_as_int(a), __float_as_int(b), false, false);
@@ -1027,8 +1029,6 @@ __device__ __forceinline__ void row16_sum_n(float* v) {
     for (int k = 0; k < N; ++k) v[k] = row16_sum(v[k]);
   }
 }
-// Packed fp32 (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth of FMAs per issue slot).
-typedef float f2v __attribute__((ext_vector_type(2)));
 // x . w over one feature chunk: even features accumulate in .x, odd ones in .y (one packed FMA per
 // feature pair), then the halves are added -- exactly the scalar two-accumulator order
 // (acc0 = x0 w0 + x2 w2 + ..., acc1 = x1 w1 + ..., acc0 + acc1).
@@ -1041,6 +1041,85 @@ __device__ __forceinline__ float chunk_dot(const float (&x)[KP], const float (&w
   float a0 = acc.x;
   if constexpr ((KP & 1) != 0) a0 = fmaf(x[KP - 1], w[KP - 1], a0);
   return a0 + acc.y;
+}
+// The middle of a hand-placed step (linear_wave_f_kernel, kHandStep: two rows per lane, five features
+// and the record's 1.0f per row, one output, loss LOSS of float targets), from the two partial logits
+// to the six column sums, as ONE block. The floating-point operations, their operands and their
+// order are those of rs16 / rs32 / row_loss / the packed backward below; what the block decides is
+// which instruction forms a value and where it is issued:
+//   - a swap exchanges two distinct registers, so a value swapped with itself needs a copy. Sum and
+//     copy (after the first swap) and scaled dL/dz and copy (before the last) each come from one packed
+//     instruction on the swap's own register pair: v_pk_add_f32 with op_sel:[0,1] op_sel_hi:[0,1]
+//     puts a + b in both halves, v_pk_mul_f32 with op_sel_hi:[0,0] puts cg * g in both; each half is
+//     the scalar operation on the same operands in the same order (the same bits, NaNs included);
+//   - a swap reads a VGPR two wait states after its VALU write. The step's independent instructions
+//     stand there instead of s_nop 1: the two gather offsets of the next batch (o0, o1 = list entry *
+//     row bytes + record offset), the select of the own row's target, the loss value; where only one
+//     is left, s_nop 0 takes the other wait state;
+//   - the products read dL/dz of the second row from the pair's high half (op_sel), no copy;
+//   - the 24 DPP adds follow stage-major as in row16_sum_n<6>; the products in front of them are
+//     ordered so that each value's first add is at least two instructions behind its product.
+// The pairs are fixed registers: inline assembly cannot name the halves of a pair operand.
+// In: zz = {zp[0], zp[1]}; o0, o1 = the next batch's list entries; wa, wb, wc = row 0's {x0, x1},
+// {x2, x3}, {x4, 1}; xa, xb, xc = row 1's. Out: o0, o1 = the gather offsets; a, b, c = the column
+// sums over the DPP row of {t0, t1}, {t2, t3}, {t4, tb}; l = the row's loss, unscaled.
+template <int LOSS>
+__device__ __forceinline__ void hand_step_2x5(f2v zz, uint32_t& o0, uint32_t& o1, f2v& a, f2v& b, f2v& c, float& l, f2v wa,
+                                              f2v wb, f2v wc, f2v xa, f2v xb, f2v xc, float y0, float y1, uint64_t own_mask,
+                                              uint32_t ldx4, uint32_t rec4, float bias, f2v cg) {
+  static_assert(LOSS == kLossCESoft || LOSS == kLossMSE, "float targets");
+  float y, t;
+#define PTDT_HS_HEAD                                                                 \
+  "v_mad_u32_u24 %[o0], %[o0], %[ld], %[rec]\n\t"                                    \
+  "v_cndmask_b32_e64 %[y], %[y0], %[y1], %[m]\n\t"                                   \
+  "v_permlane16_swap_b32 v40, v41\n\t"                                              \
+  "v_pk_add_f32 v[40:41], v[40:41], v[40:41] op_sel:[0,1] op_sel_hi:[0,1]\n\t"      \
+  "v_mad_u32_u24 %[o1], %[o1], %[ld], %[rec]\n\t"                                    \
+  "s_nop 0\n\t"                                                                     \
+  "v_permlane32_swap_b32 v40, v41\n\t"                                              \
+  "v_add_f32_e32 v40, v40, v41\n\t"                                                 \
+  "v_add_f32_e32 v40, %[bias], v40\n\t"
+#define PTDT_HS_TAIL                                                                 \
+  "s_nop 0\n\t"                                                                     \
+  "v_permlane16_swap_b32 v40, v41\n\t"                                              \
+  "v_pk_mul_f32 v[42:43], %[wa], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_mul_f32 v[44:45], %[wb], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_mul_f32 v[46:47], %[wc], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_fma_f32 v[42:43], %[xa], v[40:41], v[42:43] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  "v_pk_fma_f32 v[44:45], %[xb], v[40:41], v[44:45] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  "v_pk_fma_f32 v[46:47], %[xc], v[40:41], v[46:47] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  PTDT_HS_R16(8) PTDT_HS_R16(4) PTDT_HS_R16(2) PTDT_HS_R16(1)
+#define PTDT_HS_R16(ROR)                                                       \
+  "v_add_f32_dpp v42, v42, v42 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_add_f32_dpp v43, v43, v43 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_add_f32_dpp v44, v44, v44 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_add_f32_dpp v45, v45, v45 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_add_f32_dpp v46, v46, v46 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_add_f32_dpp v47, v47, v47 row_ror:" #ROR " row_mask:0xf bank_mask:0xf\n\t"
+#define PTDT_HS_OPS                                                                                                    \
+  : "+{v[40:41]}"(zz), [o0] "+v"(o0), [o1] "+v"(o1), "=&{v[42:43]}"(a), "=&{v[44:45]}"(b), "=&{v[46:47]}"(c),          \
+    [l] "=&v"(l), [y] "=&v"(y), [t] "=&v"(t)                                                                           \
+  : [wa] "v"(wa), [wb] "v"(wb), [wc] "v"(wc), [xa] "v"(xa), [xb] "v"(xb), [xc] "v"(xc), [y0] "v"(y0), [y1] "v"(y1),    \
+    [m] "s"(own_mask), [ld] "s"(ldx4), [rec] "v"(rec4), [bias] "v"(bias), [cg] "v"(cg)
+  if constexpr (LOSS == kLossCESoft) {
+    // log_softmax of one class ls0 = z - z (0, or NaN); g = fma(ls0, y, 0); l = -y ls0
+    asm volatile(PTDT_HS_HEAD
+                 "v_sub_f32_e32 %[t], v40, v40\n\t"
+                 "v_fma_f32 v40, %[t], %[y], 0\n\t"
+                 "v_pk_mul_f32 v[40:41], %[cg], v[40:41] op_sel_hi:[0,0]\n\t"
+                 "v_mul_f32_e64 %[l], %[t], -%[y]\n\t" PTDT_HS_TAIL PTDT_HS_OPS);
+  } else {
+    // df = z - y; g = 2 df; l = fma(df, df, 0)
+    asm volatile(PTDT_HS_HEAD
+                 "v_sub_f32_e32 %[t], v40, %[y]\n\t"
+                 "v_mul_f32_e32 v40, 2.0, %[t]\n\t"
+                 "v_pk_mul_f32 v[40:41], %[cg], v[40:41] op_sel_hi:[0,0]\n\t"
+                 "v_fma_f32 %[l], %[t], %[t], 0\n\t" PTDT_HS_TAIL PTDT_HS_OPS);
+  }
+#undef PTDT_HS_R16
+#undef PTDT_HS_HEAD
+#undef PTDT_HS_TAIL
+#undef PTDT_HS_OPS
 }
 // SGD update kinds of the step loop (one loop instantiation each; no per-element branch)
 constexpr int kSgdPlain = 0;  // no momentum, no weight decay: w -= lr * g (the reference's SGD(lr))
@@ -1114,6 +1193,10 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   constexpr bool IMG = LEAN && DOUT == 1 && LOSS != kLossCEIndex;
   constexpr bool PKT = IMG && (KP & 1) != 0;  // packed backward tail {x[KP-1], 1} . {g, g}
   using BatchT = Batch<R, KP, DOUT, RY, IMG>;
+  // The hand-placed step (train_hand, hand_step_2x5): the unchecked group body of the two-body image
+  // kernels of Linear(17..20, 1) at B = 32 without the in-kernel all-reduce. Every other body and every
+  // other kernel keeps the compiler's step (train).
+  constexpr bool kHandStep = IMG && SCATTER && R == 2 && KP == 5 && !AR && lean_two_bodies(R, KP, DOUT, VAR, AR);
   extern __shared__ int elist[];
   // The kernel arguments the prologue reads are loaded here in one batch, pinned by the empty asm
   // (one wait for all), before the first branch. Left to the compiler, each scalar load followed
@@ -1757,7 +1840,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         Wb[c] = hb ? Wb[c] : 0.f;
       }
     }
-    ++opt_step;
+    if constexpr (VAR != kWaveLeanPlain) ++opt_step;  // plain SGD never reads it: formed after the loop
     // the DDP bucket (a.G) keeps the last step's averaged gradients: register
     // copies here (the unrolled loop keeps only the last), one store at the end
 #pragma unroll
@@ -1888,7 +1971,108 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   using Plain = std::integral_constant<int, kSgdPlain>;
   using NoMom = std::integral_constant<int, kSgdNoMom>;
   using Mom = std::integral_constant<int, kSgdMom>;
-  if constexpr (VAR == kWaveLeanPlain) {  // the plan's loop is the only one in a lean kernel
+  if constexpr (kHandStep) {
+    // The unchecked group body with the step placed by hand; the checked body and the tail are
+    // run_lean's. One step, for batch f (the floating-point operations of train, in its order):
+    //   - one wait for the batch and for the list entries read during the previous step;
+    //   - the forward products (chunk_dot), then hand_step_2x5 with the next list read issued in
+    //     front of it (it has the whole block to land in);
+    //   - behind the block the loss share and the gather of the batch three steps ahead into f, then
+    //     the update: five instructions stand between the block and the first VALU instruction that
+    //     reads what it wrote (the compiler puts s_nop in front of a VALU instruction that reads a
+    //     register an asm statement has just written).
+    using SgdTag = std::integral_constant<int, VAR == kWaveLeanPlain ? kSgdPlain : kSgdMom>;
+    using BT = RowRecords<R, KP>;
+    static_assert(BT::NV == 2, "two 16-byte loads per record");
+    f2v cg2 = {gs_full, gs_full};  // a full batch's gradient scale as a register pair
+    asm volatile("" : "+v"(cg2));
+    const uint64_t own_m0 = __builtin_amdgcn_ballot_w64(own_b0);  // own_b0 as a lane mask, for the block's select
+    auto train_hand = [&](BatchT& f) {
+      // the pin only reads (see above); the scheduling barrier keeps every use of the batch behind the wait
+      asm volatile("" ::"v"(f.img[1][1]), "v"(f.img[1][0]), "v"(f.img[0][1]), "v"(f.img[0][0]), "v"(sel_next[0]), "v"(sel_next[1]));
+      __builtin_amdgcn_sched_barrier(0);
+      float x[R][KP], one[R], ypk[R];
+#pragma unroll
+      for (int rho = 0; rho < R; ++rho) {
+#pragma unroll
+        for (int k = 0; k < KP; ++k) x[rho][k] = f.img[rho][k >> 2][k & 3];
+        one[rho] = f.img[rho][KP >> 2][KP & 3];
+        ypk[rho] = f.img[rho][wave_image_y_slot(KP) >> 2][wave_image_y_slot(KP) & 3];
+      }
+      const float zp0 = chunk_dot<KP>(x[0], W[0]), zp1 = chunk_dot<KP>(x[1], W[0]);
+      uint32_t o0 = (uint32_t)sel_next[0], o1 = (uint32_t)sel_next[1];
+      read_run();
+      __builtin_amdgcn_sched_barrier(0);
+      f2v hs[3];
+      float lraw;
+      hand_step_2x5<LOSS>(f2v{zp0, zp1}, o0, o1, hs[0], hs[1], hs[2], lraw, f2v{x[0][0], x[0][1]}, f2v{x[0][2], x[0][3]},
+                          f2v{x[0][4], one[0]}, f2v{x[1][0], x[1][1]}, f2v{x[1][2], x[1][3]}, f2v{x[1][4], one[1]}, ypk[0],
+                          ypk[1], own_m0, ldx4, rec4, Wb[0], cg2);
+      *rp = lraw;
+      rp += 64;
+#pragma unroll
+      for (int v = 0; v < BT::NV; ++v) {
+        f.img[0][v] = __builtin_bit_cast(typename BT::rec4, __builtin_amdgcn_raw_buffer_load_b128(xrs, o0 + 16 * v, 0, 0));
+        f.img[1][v] = __builtin_bit_cast(typename BT::rec4, __builtin_amdgcn_raw_buffer_load_b128(xrs, o1 + 16 * v, 0, 0));
+      }
+      // the offsets stay live over the loads: in a register that one of the loads writes, the compiler
+      // pads the loads with s_nop
+      asm volatile("" ::"v"(o0), "v"(o1));
+      __builtin_amdgcn_sched_barrier(0);
+      const float gr[KP + 1] = {hs[0].x, hs[0].y, hs[1].x, hs[1].y, hs[2].x, hs[2].y};
+      if constexpr (VAR == kWaveLeanPlain) {  // train's packed plain SGD: [W[0][0 .. 4], Wb[0]] in pairs
+        float u[KP + 1];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) u[k] = W[0][k];
+        u[KP] = Wb[0];
+#pragma unroll
+        for (int k = 0; k + 1 < KP + 1; k += 2) {
+          const f2v nl = {-lr, k + 1 == KP ? -lr_b : -lr};
+          const f2v r = __builtin_elementwise_fma(nl, f2v{gr[k], gr[k + 1]}, f2v{u[k], u[k + 1]});
+          u[k] = r.x;
+          u[k + 1] = r.y;
+        }
+#pragma unroll
+        for (int k = 0; k < KP; ++k) W[0][k] = u[k];
+        Wb[0] = u[KP];
+      } else {  // train's momentum update
+        const bool first = opt_step == 0;
+        auto upd = [&](float& w, float& m, float g) {
+          float d = fmaf(wd, w, g);
+          const float mb = first ? d : fmaf(mu, m, (1.f - damp) * d);
+          m = mb;
+          d = nesterov ? fmaf(mu, mb, d) : mb;
+          w = fmaf(-lr, d, w);
+        };
+#pragma unroll
+        for (int k = 0; k < KP; ++k) upd(W[0][k], M[0][k], gr[k]);
+        upd(Wb[0], Mb[0], gr[KP]);
+        Wb[0] = hb ? Wb[0] : 0.f;
+        ++opt_step;
+      }
+#pragma unroll
+      for (int k = 0; k < KP; ++k) Gk[0][k] = gr[k];
+      Gbk[0] = gr[KP];
+    };
+    done = wave_loop_run(
+        sch, n,
+        [&]() {
+#pragma unroll
+          for (int u = 0; u < kNB; ++u) train_hand(buf[u]);
+          return true;
+        },
+        [&](WaveLoopSchedule& c) {
+#pragma unroll
+          for (int u = 0; u < kNB; ++u) {
+            train(buf[u], 0, SgdTag{}, std::true_type{});
+            load_batch(buf[u], sel_next, sel_y_next, B);
+            read_checked();
+            if (c.slot_done()) rp = lring + lane;
+          }
+          return true;
+        },
+        [&](WaveLoopSchedule& c, int left) { return lean_tail(c, left, SgdTag{}); });
+  } else if constexpr (VAR == kWaveLeanPlain) {  // the plan's loop is the only one in a lean kernel
     run_lean(Plain{});
   } else if constexpr (VAR == kWaveLeanMom) {
     run_lean(Mom{});
@@ -1927,6 +2111,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     const int64_t pos = pos0 + done;
     pa.cursor[0] = (int)(pos / S);
     pa.cursor[1] = (int)(pos % S);
+    if constexpr (VAR == kWaveLeanPlain) opt_step += done;  // one per step trained
     if (opt_step_p != nullptr) *opt_step_p = opt_step;
     if (AR) *seq_p = seq;
     if (tk.on) {
