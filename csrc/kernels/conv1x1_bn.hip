@@ -27,46 +27,18 @@
 #include "common.h"
 #include "handoff.h"
 #include "kernels.h"
+#include "lds_tile.h"
 
 namespace ptdt {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// workgroup barrier without __syncthreads' fence (which would drain every in-flight DMA and store):
-// LDS traffic retired, then s_barrier
+// LDS traffic retired, then the workgroup barrier
 __device__ __forceinline__ void bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// 16-B chunk c of LDS row r (rows of K bf16) is stored in slot swz(r, c) of the row, so the 16 lanes of
-// a fragment read (16 consecutive rows, one chunk) hit 16 distinct 16-B slots
-template <int K>
-__device__ __forceinline__ int swz(int r, int c) {
-  // rows of 128 B (K = 64): XOR the 8 chunks of the row by (r >> 1) & 7 (two rows share a 256-B bank row);
-  // rows of >= 256 B: XOR the chunk index by r & 15, so 16 consecutive rows land on 16 distinct 16-B slots
-  // of the bank row (the (r >> 1) & 7 form left two rows of a fragment read on one bank: PMC
-  // SQ_LDS_BANK_CONFLICT 3.6-7.2M cycles per launch, profiles/r3_pmc_convbn_stream.md). An involution.
-  if constexpr (K >= 128) return c ^ (r & 15);
-  else return (c & ~7) | ((c & 7) ^ ((r >> 1) & 7));
-}
-template <int K>
-__device__ __forceinline__ int lds_off(int r, int c) {
-  return r * (K * 2) + swz<K>(r, c) * 16;
+  lds_wait();
+  wg_barrier();
 }
 
 // compile-time loop: f(std::integral_constant<int, i>) for i = 0 .. n-1
@@ -108,9 +80,6 @@ struct C1 {
   static_assert(2 * NW * NSL * 4 + 16 <= NBUF * AB, "cross-wave statistics scratch");
 };
 
-// weight row of col-frag j's MFMA row fr (see the header): channel 32p + 8(fr/4) + 4(j%2) + fr%4
-__device__ __forceinline__ int w_channel(int j, int fr) { return 32 * (j >> 1) + 8 * (fr >> 2) + 4 * (j & 1) + (fr & 3); }
-
 template <int K, int N, int NW, int NB, int NS>
 __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uint16_t* __restrict__ X,
                                                                        const uint16_t* __restrict__ W,
@@ -131,20 +100,17 @@ __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uin
   const int G = (int)gridDim.x / NS;  // row workgroups
   const int n0 = slab * NSL;
 
-  // X block t of this workgroup: rows (blockIdx.x + t*G) * BM ..; rows past M clamp to M-1 (computed,
-  // never stored, not counted)
+  // X block t of this workgroup: rows (rwg + t*G) * BM ..; rows past M clamp to M-1 (computed, never
+  // stored, not counted)
   auto stage = [&](int t) {
-    const int blk = rwg + t * G;
-    const int row0 = blk * S::BM;
+    const int row0 = (rwg + t * G) * S::BM;
     uint8_t* dst0 = al + (t % S::NBUF) * S::AB;
+    // stage_rows' loop on the thread index itself: with wid * 64 + lane the compiler keeps the wave part of
+    // every round's address in registers of its own, 8-36 VGPRs and a wave of occupancy in five instances
 #pragma unroll
-    for (int i = 0; i < S::DMA; ++i) {
-      const int p = i * S::NT + tid;  // 16-B chunk of the block image (linear LDS order)
-      const int r = p / (K / 8), slot = p % (K / 8);
-      // the chunk stored in LDS slot `slot` of row r is logical chunk c (the swizzle is an involution)
-      const int c = swz<K>(r, slot);
-      const int gr = min(row0 + r, M - 1);
-      const uint16_t* g = X + (int64_t)gr * K + c * 8;
+    for (int i = 0; i < stage_rounds<S::BM, K * 2, S::NT>(); ++i) {
+      const TileChunk s = staged_chunk<K * 2>(i * S::NT + tid);
+      const uint16_t* g = X + (int64_t)min(row0 + s.r, M - 1) * K + s.c * 8;
       __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)(dst0 + (i * S::NT + wid * 64) * 16), 16, 0, 0);
     }
   };
@@ -156,8 +122,8 @@ __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uin
   // resident weights in MFMA row order (plain loads + LDS stores, once)
   for (int p = tid; p < NSL * (K / 8); p += S::NT) {
     const int r = p / (K / 8), c = p % (K / 8);  // LDS row r = (col-frag j, MFMA row fr)
-    const int ch = n0 + w_channel(r >> 4, r & 15);
-    *reinterpret_cast<uint4*>(wl + lds_off<K>(r, c)) = *reinterpret_cast<const uint4*>(W + (int64_t)ch * K + c * 8);
+    const int ch = n0 + pair_channel(r >> 4, r & 15);  // col-frags 2p, 2p+1: 8 channels per lane group
+    *reinterpret_cast<uint4*>(wl + tile_off<K * 2>(r, c)) = *reinterpret_cast<const uint4*>(W + (int64_t)ch * K + c * 8);
   }
   // pivots (the running mean, or 0) for the lane's channels 32p + 8fq + q, spread over the 16 lanes of
   // its DPP row: value i = 8p + q sits in register i / 16 of lane fr = i % 16 and is broadcast with
@@ -192,7 +158,7 @@ __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uin
     bf16x8_t xb[S::KS];
 #pragma unroll
     for (int ks = 0; ks < S::KS; ++ks)
-      xb[ks] = *reinterpret_cast<const bf16x8_t*>(at + lds_off<K>(wid * 16 + fr, ks * 4 + fq));
+      xb[ks] = *reinterpret_cast<const bf16x8_t*>(at + tile_off<K * 2>(wid * 16 + fr, ks * 4 + fq));
     const int m = (rwg + t * G) * S::BM + wid * 16 + fr;
     const bool valid = m < M;
     // a row past M multiplied the clamped row M-1: it stores row M-1's identical bytes there, so
@@ -208,7 +174,7 @@ __global__ void __launch_bounds__(NW * 64, 2) conv1x1_bn_stream_kernel(const uin
 #pragma unroll
         for (int j = 0; j < 2 * S::CP; ++j) {
           const int jj = ch * 2 * S::CP + j;
-          const bf16x8_t wa = *reinterpret_cast<const bf16x8_t*>(wl + lds_off<K>(jj * 16 + fr, ks * 4 + fq));
+          const bf16x8_t wa = *reinterpret_cast<const bf16x8_t*>(wl + tile_off<K * 2>(jj * 16 + fr, ks * 4 + fq));
           acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb[ks], acc[j], 0, 0, 0);
         }
       static_for<0, S::CP>([&](auto ppc) {

@@ -25,12 +25,11 @@
 //     16.3 ms unfused, profiles/r4_resnet_step.md.)
 #include "common.h"
 #include "kernels.h"
+#include "lds_tile.h"
 
 namespace ptdt {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
@@ -41,10 +40,6 @@ typedef __attribute__((address_space(1))) float gfloat;
 constexpr int kBwdWaves = 4;
 constexpr int kBwdThreads = 64 * kBwdWaves;
 constexpr int kBwdBM = 64;  // rows per block (16 per wave for the data gradient)
-
-// input channel of row i of data-gradient A tile j (a pair of tiles covers 32 channels; lane group q
-// of the pair holds channels 32p + 8q .. +7)
-__device__ __forceinline__ int k_of(int j, int i) { return 32 * (j >> 1) + 8 * (i >> 2) + 4 * (j & 1) + (i & 3); }
 
 template <int K, int N>
 struct Cb {
@@ -90,7 +85,7 @@ __global__ void __launch_bounds__(kBwdThreads, 2) conv1x1_bwd_kernel(
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int k = kc * 8 + u;
-      // LDS row r of tile j holds channel k_of(j, i): r = 16 j + i with k_of(j, i) = k
+      // LDS row r = 16 j + i of data-gradient A tile j holds input channel pair_channel(j, i) = k
       const int j = 2 * (k >> 5) + ((k >> 2) & 1), i = 4 * ((k >> 3) & 3) + (k & 3);
       *reinterpret_cast<uint16_t*>(wt + (16 * j + i) * S::SWT + n * 2) = (uint16_t)(v[u >> 1] >> (16 * (u & 1)));
     }

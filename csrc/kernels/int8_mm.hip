@@ -15,20 +15,18 @@
 //
 // int8_mm, tiled path (K % 128 == 0): 128x128 output tile per workgroup of 4 waves (2x2,
 // 64x64 each = 4x4 MFMA tiles), K in 128-byte tiles staged global -> LDS with
-// global_load_lds_dwordx4 (16 B per lane, no VGPR round trip), double-buffered: tile k+1's
-// DMA is in flight (counted vmcnt) while tile k is multiplied. A tile is rows x 8 chunks
-// of 16 B; chunk c of row r lives in slot c ^ ((r >> 1) & 7), so the 16 rows read by one
-// ds_read_b128 hit 16 distinct slots (conflict-free) -- the layout of gemm_big.hip's bf16
-// tiles, whose 64-element K-tile is the same 128 bytes. Workgroup ids are XCD-remapped.
+// global_load_lds_dwordx4 into swizzled 128-byte rows, double-buffered -- the tiles, staging
+// and K-loop protocols of gemm_big.hip's bf16 kernels (lds_tile.h), whose 64-element K-tile is
+// the same 128 bytes. Workgroup ids are XCD-remapped.
 // Shapes with >= 256 256x256 tiles take the 8-wave 256x256 ping-pong variant (i8_mm_t256_kernel).
 // Direct path (other K % 16 == 0): fragments straight from global memory, 64x64 tiles.
 #include "common.h"
 #include "kernels.h"
+#include "lds_tile.h"
 
 namespace ptdt {
 namespace {
 
-using i32x4 = __attribute__((ext_vector_type(4))) int;
 constexpr int kThreads = 256;
 
 // Column absmax over a chunk of rows: thread = one column (coalesced rows), grid (column
@@ -174,28 +172,15 @@ constexpr int TILE_BYTES = TM * BKB;                  // one operand tile (16 Ki
 constexpr int BUF = 2 * TILE_BYTES;                   // A + B
 constexpr int LDS_BYTES = 2 * BUF;                    // double buffered: 64 KiB (2 workgroups per CU)
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
 // LDS-DMA of one ROWS x 128-byte operand tile (rows row0.., bytes k0..k0+127) by THREADS threads
 template <int ROWS, int THREADS>
 __device__ __forceinline__ void stage_i8(const int8_t* __restrict__ src, int K, int row0, int nrows, int k0,
                                          uint8_t* lds_tile, int wid, int lane) {
-#pragma unroll
-  for (int i = 0; i < ROWS * BKB / (THREADS * 16); ++i) {
-    const int p = i * THREADS + wid * 64 + lane;  // linear 16-B chunk of the tile image
-    const int r = p >> 3, slot = p & 7;
-    const int ch = slot ^ ((r >> 1) & 7);       // logical 16-B k-chunk stored in this slot
-    const int gr = min(row0 + r, nrows - 1);    // clamp: edge rows are computed, never stored
-    const int8_t* gsrc = src + (int64_t)gr * K + k0 + ch * 16;
-    uint8_t* dst = lds_tile + (i * THREADS + wid * 64) * 16;  // wave-uniform base; hardware adds lane * 16
-    __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)dst, 16, 0, 0);
-  }
+  stage_rows<ROWS, BKB, THREADS>(src, K, k0, lds_tile, wid, lane, [=](int r) { return min(row0 + r, nrows - 1); });
 }
 
 __device__ __forceinline__ i32x4 frag(const uint8_t* lds_tile, int row, int ch) {
-  const int slot = ch ^ ((row >> 1) & 7);
-  return *reinterpret_cast<const i32x4*>(lds_tile + row * BKB + slot * 16);
+  return read_frag<i32x4, BKB>(lds_tile, row, ch);
 }
 
 __global__ void __launch_bounds__(kThreads) i8_mm_tiled_kernel(const int8_t* __restrict__ A,
@@ -220,17 +205,7 @@ __global__ void __launch_bounds__(kThreads) i8_mm_tiled_kernel(const int8_t* __r
     stage_i8<TM, kThreads>(A, K, m0, e.M, kt * BKB, buf, wid, lane);
     stage_i8<TN, kThreads>(B, K, n0, e.N, kt * BKB, buf + TILE_BYTES, wid, lane);
   };
-  stage(0, smem);
-  for (int kt = 0; kt < nk; ++kt) {
-    const uint8_t* cur = smem + (kt & 1) * BUF;
-    if (kt + 1 < nk) {
-      stage(kt + 1, smem + ((kt + 1) & 1) * BUF);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile kt landed (2 x 4 DMAs), kt+1 in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();  // every wave's DMA of tile kt is visible
-    __builtin_amdgcn_sched_barrier(0);
+  auto mult = [&](const uint8_t* cur) {  // read, then multiply, one K-tile
     i32x4 a[2][FI], b[2][FJ];
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {  // two 64-byte halves of the K-tile
@@ -246,19 +221,16 @@ __global__ void __launch_bounds__(kThreads) i8_mm_tiled_kernel(const int8_t* __r
 #pragma unroll
         for (int j = 0; j < FJ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[kb][i], b[kb][j], acc[i][j], 0, 0, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();  // buffer kt & 1 free for tile kt + 2
-  }
+  };
+  kloop_double_buffered<8>(nk, smem, BUF, stage, mult);  // 2 x 4 DMAs per thread and K-tile
   i8_epilogue<FI, FJ>(e, acc, m0 + wr * 64, n0 + wc * 64, c, g);
 }
 
 // 256x256 tile, 8 waves (2 M x 4 N, 128x64 each = 8x4 MFMA tiles), 128 KiB LDS (one workgroup
-// per CU), ping-pong wave pairs as gemm_big.hip's SCHED 1: the two waves sharing a SIMD (w and
-// w + 4, M halves wr = 0 / 1) run half a K-tile apart, so while one multiplies from registers
-// its partner reads the next fragments from LDS and the SIMD's matrix pipe stays fed. Tile
-// t+1's DMA is issued at the start of slot 2t and retired (vmcnt(0)) before the barrier that
-// closes slot 2t+1.
+// per CU), ping-pong wave pairs (M halves wr = 0 / 1 as leader / follower): the slot protocol of
+// lds_tile.h's kloop_pingpong, written out here. At 256 VGPRs this kernel took a second spill
+// and ran 1.5 % slower on the shared loop (profiles/lds_tile_pieces.md); a change to the
+// protocol goes into both.
 constexpr int TB = 256, TB_TILE = TB * BKB, TB_BUF = 2 * TB_TILE, TB_LDS = 2 * TB_BUF;  // 128 KiB
 __global__ void __launch_bounds__(512) i8_mm_t256_kernel(const int8_t* __restrict__ A, const int8_t* __restrict__ B,
                                                          int K, I8Epi e, int tm, int tn) {
@@ -301,35 +273,30 @@ __global__ void __launch_bounds__(512) i8_mm_t256_kernel(const int8_t* __restric
           acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[kb][i], b[kb][j], acc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto bar = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
   stage(0, smem);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  bar();  // tile 0 visible
+  vm_wait<0>();
+  wg_barrier();  // tile 0 visible
   if (wr == 0) {  // leader: slot 2kt reads tile kt, slot 2kt+1 multiplies it
     for (int kt = 0; kt < nk; ++kt) {
       const uint8_t* cur = smem + (kt & 1) * TB_BUF;
       if (kt + 1 < nk) stage(kt + 1, smem + ((kt + 1) & 1) * TB_BUF);
       read(cur);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bar();
+      lds_wait();
+      wg_barrier();
       mma();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile kt+1 landed (own DMAs)
-      bar();
+      vm_wait<0>();  // tile kt+1 landed (own DMAs)
+      wg_barrier();
     }
   } else {  // follower: slot 2kt multiplies tile kt-1, slot 2kt+1 reads tile kt
     for (int kt = 0; kt < nk; ++kt) {
       const uint8_t* cur = smem + (kt & 1) * TB_BUF;
       if (kt + 1 < nk) stage(kt + 1, smem + ((kt + 1) & 1) * TB_BUF);
       if (kt > 0) mma();
-      bar();
+      wg_barrier();
       read(cur);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      bar();
+      lds_wait();
+      vm_wait<0>();
+      wg_barrier();
     }
     mma();
   }

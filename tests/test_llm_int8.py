@@ -25,16 +25,23 @@ def test_llm_int8_reference_cpu_tracks_fp32_and_handles_outliers():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,N,K", [(70, 50, 128), (64, 64, 64), (5, 130, 48), (129, 17, 256),
-                                   (256, 384, 512), (130, 260, 384), (1, 300, 1024), (300, 7, 128)])
+                                   (256, 384, 512), (130, 260, 384), (1, 300, 1024), (300, 7, 128),
+                                   (3845, 4090, 384)])
 def test_int8_mm_exact_integer_products(dev, M, N, K):
     """v_mfma_i32_16x16x64_i8 operand map: exact int32 products (scales 1, f32 out); K % 128 == 0
-    runs the LDS-staged tiled kernel (edge tiles included), the rest the direct one."""
+    runs the LDS-staged tiled kernel (edge tiles included), the rest the direct one. The last shape is
+    16 x 16 = 256 tiles of 256x256, ragged in both directions, three K-tiles: the ping-pong kernel."""
     from pytorch_distributed_training_tutorials_amd._ext import native
 
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randint(-127, 128, (M, K), generator=g, dtype=torch.int8)
     B = torch.randint(-127, 128, (N, K), generator=g, dtype=torch.int8)
-    ref = (A.long() @ B.long().t()).float()
+    # the large shape: every partial sum is an integer below 127^2 K < 2^24, so fp32 is exact in any order
+    # (bit for bit the int64 product, 60 times sooner); the others keep the int64 product
+    if M * N > 1 << 20 and 127 * 127 * K < 1 << 24:
+        ref = A.float() @ B.float().t()
+    else:
+        ref = (A.long() @ B.long().t()).float()
     y = native().int8_mm(A.to(dev), torch.ones(M, device=dev), B.to(dev), torch.ones(N, device=dev))
     assert torch.equal(y.cpu(), ref)
 
