@@ -1117,9 +1117,101 @@ __device__ __forceinline__ void hand_step_2x5(f2v zz, uint32_t& o0, uint32_t& o1
                  "v_fma_f32 %[l], %[t], %[t], 0\n\t" PTDT_HS_TAIL PTDT_HS_OPS);
   }
 #undef PTDT_HS_R16
-#undef PTDT_HS_HEAD
 #undef PTDT_HS_TAIL
 #undef PTDT_HS_OPS
+}
+// Row lanes of the reduce-scattered column sums (hand_step_2x5_rs): value k of {t0 .. t4, tb} has its
+// total in lanes 4 * bank .. 4 * bank + 3 of gx (k < 4) or gy (k >= 4); the update and the run-end
+// gradient read it from lane kHsBcast[k] with row_newbcast. Any lane of the bank holds the total (the
+// same bits where it is finite). Which lane is read decides only which leaf's NaN comes out of sixteen
+// different ones (tools/wave_colsum_order_check.cpp lists it per lane and operand rule).
+constexpr int kHsBcast[6] = {0, 10, 4, 12, 0, 10};
+// hand_step_2x5 for the lean-plain kernels: the column sums as a reduce-scatter. All sixteen lanes of
+// a DPP row holding all six sums is an all-reduce (24 adds); the update needs each sum once per row,
+// and v_fmac_f32_dpp reads it from one lane (row_newbcast). So the tree keeps each value in a shrinking
+// share of the row: 13 adds. The pairs added at each stage are row16_sum_n's ({i, i + 8}, {i, i + 4},
+// {i, i + 2}, {i, i + 1}), so a finite total has its bits.
+//   stage 1  row_ror:8 into one register per pair of values: bank_mask 0x3 writes the first value's
+//            half sums to lanes 0-7, 0xc the second's to lanes 8-15             -> AB, CD, EF
+//   stage 2  row_shl:4 under bank_mask 0x5 (banks 0, 2 add banks 1, 3), row_shr:4 under 0xa (banks
+//            1, 3 add banks 0, 2)                -> gx = banks [A, C, B, D], gy = banks [E, -, F, -]
+//   stage 3  quad_perm:[2,3,0,1], stage 4 quad_perm:[1,0,3,2] on gx and gy
+// A DPP read stands two instructions behind the VALU write of its source. Stages 3 and 4 have two
+// instructions each: the loss value (which leaves the wait states of the last swap to an s_nop 1) and
+// one s_nop 0 take the third place.
+// Out: gx, gy as above; l, o0, o1 as hand_step_2x5.
+template <int LOSS>
+__device__ __forceinline__ void hand_step_2x5_rs(f2v zz, uint32_t& o0, uint32_t& o1, float& gx, float& gy, float& l, f2v wa,
+                                                 f2v wb, f2v wc, f2v xa, f2v xb, f2v xc, float y0, float y1,
+                                                 uint64_t own_mask, uint32_t ldx4, uint32_t rec4, float bias, f2v cg) {
+  static_assert(LOSS == kLossCESoft || LOSS == kLossMSE, "float targets");
+  float y, t;
+#define PTDT_HS_S1(DST, V0, V1)                                                                \
+  "v_add_f32_dpp " DST ", " V0 ", " V0 " row_ror:8 row_mask:0xf bank_mask:0x3\n\t"              \
+  "v_add_f32_dpp " DST ", " V1 ", " V1 " row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+#define PTDT_HS_TAIL_RS(LOSS_VALUE)                                                             \
+  "s_nop 1\n\t"                                                                                 \
+  "v_permlane16_swap_b32 v40, v41\n\t"                                                          \
+  "v_pk_mul_f32 v[42:43], %[wa], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_mul_f32 v[44:45], %[wb], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_mul_f32 v[46:47], %[wc], v[40:41] op_sel_hi:[1,0]\n\t"                                  \
+  "v_pk_fma_f32 v[42:43], %[xa], v[40:41], v[42:43] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  "v_pk_fma_f32 v[44:45], %[xb], v[40:41], v[44:45] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  "v_pk_fma_f32 v[46:47], %[xc], v[40:41], v[46:47] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"       \
+  PTDT_HS_S1("v42", "v42", "v43") PTDT_HS_S1("v44", "v44", "v45") PTDT_HS_S1("v46", "v46", "v47") \
+  "v_add_f32_dpp v42, v42, v42 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                        \
+  "v_add_f32_dpp v42, v44, v44 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                        \
+  "v_add_f32_dpp v46, v46, v46 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                        \
+  LOSS_VALUE                                                                                    \
+  "v_add_f32_dpp v42, v42, v42 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"              \
+  "v_add_f32_dpp v46, v46, v46 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"              \
+  "s_nop 0\n\t"                                                                                 \
+  "v_add_f32_dpp v42, v42, v42 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"              \
+  "v_add_f32_dpp v46, v46, v46 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+#define PTDT_HS_OPS_RS                                                                                                 \
+  : "+{v[40:41]}"(zz), [o0] "+v"(o0), [o1] "+v"(o1), "=&{v42}"(gx), "=&{v46}"(gy), [l] "=&v"(l), [y] "=&v"(y),         \
+    [t] "=&v"(t)                                                                                                       \
+  : [wa] "v"(wa), [wb] "v"(wb), [wc] "v"(wc), [xa] "v"(xa), [xb] "v"(xb), [xc] "v"(xc), [y0] "v"(y0), [y1] "v"(y1),    \
+    [m] "s"(own_mask), [ld] "s"(ldx4), [rec] "v"(rec4), [bias] "v"(bias), [cg] "v"(cg)                                 \
+  : "v43", "v44", "v45", "v47"
+  if constexpr (LOSS == kLossCESoft) {
+    asm volatile(PTDT_HS_HEAD
+                 "v_sub_f32_e32 %[t], v40, v40\n\t"
+                 "v_fma_f32 v40, %[t], %[y], 0\n\t"
+                 "v_pk_mul_f32 v[40:41], %[cg], v[40:41] op_sel_hi:[0,0]\n\t"
+                 PTDT_HS_TAIL_RS("v_mul_f32_e64 %[l], %[t], -%[y]\n\t") PTDT_HS_OPS_RS);
+  } else {
+    asm volatile(PTDT_HS_HEAD
+                 "v_sub_f32_e32 %[t], v40, %[y]\n\t"
+                 "v_mul_f32_e32 v40, 2.0, %[t]\n\t"
+                 "v_pk_mul_f32 v[40:41], %[cg], v[40:41] op_sel_hi:[0,0]\n\t"
+                 PTDT_HS_TAIL_RS("v_fma_f32 %[l], %[t], %[t], 0\n\t") PTDT_HS_OPS_RS);
+  }
+#undef PTDT_HS_S1
+#undef PTDT_HS_TAIL_RS
+#undef PTDT_HS_OPS_RS
+#undef PTDT_HS_HEAD
+}
+// Plain SGD on the reduce-scattered sums: w_k += total_k * (-lr), the total read from its lane
+// (kHsBcast) by the multiply itself. fma(g, -lr, w) has the bits of the packed update's
+// fma(-lr, g, w). The bias has its own step (-lr, or -0 without a bias: no select).
+// The weights stay in the pairs the forward products read ({w0, w1}, {w2, w3}); fixed registers, since
+// inline assembly cannot name the halves of a pair operand (an operand per half makes the compiler
+// copy the halves out and back around the statement).
+__device__ __forceinline__ void hand_sgd_bcast(f2v& w01, f2v& w23, float& w4, float& wbias, float gx, float gy, float nlr,
+                                               float nlr_b) {
+  static_assert(kHsBcast[0] == 0 && kHsBcast[1] == 10 && kHsBcast[2] == 4 && kHsBcast[3] == 12 && kHsBcast[4] == 0 &&
+                    kHsBcast[5] == 10,
+                "the lanes below");
+  asm volatile(
+      "v_fmac_f32_dpp v48, %[gx], %[nlr] row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp v49, %[gx], %[nlr] row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp v50, %[gx], %[nlr] row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp v51, %[gx], %[nlr] row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[w4], %[gy], %[nlr] row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[wb], %[gy], %[nlrb] row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+      : "+{v[48:49]}"(w01), "+{v[50:51]}"(w23), [w4] "+v"(w4), [wb] "+v"(wbias)
+      : [gx] "v"(gx), [gy] "v"(gy), [nlr] "v"(nlr), [nlrb] "v"(nlr_b));
 }
 // SGD update kinds of the step loop (one loop instantiation each; no per-element branch)
 constexpr int kSgdPlain = 0;  // no momentum, no weight decay: w -= lr * g (the reference's SGD(lr))
@@ -1195,7 +1287,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   using BatchT = Batch<R, KP, DOUT, RY, IMG>;
   // The hand-placed step (train_hand, hand_step_2x5): the unchecked group body of the two-body image
   // kernels of Linear(17..20, 1) at B = 32 without the in-kernel all-reduce. Every other body and every
-  // other kernel keeps the compiler's step (train).
+  // other kernel keeps the compiler's step (train). The lean-plain ones add the column sums as a
+  // reduce-scatter and update from its lanes (hand_step_2x5_rs, hand_sgd_bcast; profiles/wave_colsum_scatter.md).
   constexpr bool kHandStep = IMG && SCATTER && R == 2 && KP == 5 && !AR && lean_two_bodies(R, KP, DOUT, VAR, AR);
   extern __shared__ int elist[];
   // The kernel arguments the prologue reads are loaded here in one batch, pinned by the empty asm
@@ -1987,6 +2080,10 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     f2v cg2 = {gs_full, gs_full};  // a full batch's gradient scale as a register pair
     asm volatile("" : "+v"(cg2));
     const uint64_t own_m0 = __builtin_amdgcn_ballot_w64(own_b0);  // own_b0 as a lane mask, for the block's select
+    // lean-plain: the scattered column sums of the last hand step (hand_step_2x5_rs), and the steps
+    // -lr, -lr_b as registers for the update that reads them
+    float hgx = 0.f, hgy = 0.f, nlr = -lr, nlr_b = -lr_b;
+    if constexpr (VAR == kWaveLeanPlain) asm volatile("" : "+v"(nlr), "+v"(nlr_b));
     auto train_hand = [&](BatchT& f) {
       // the pin only reads (see above); the scheduling barrier keeps every use of the batch behind the wait
       asm volatile("" ::"v"(f.img[1][1]), "v"(f.img[1][0]), "v"(f.img[0][1]), "v"(f.img[0][0]), "v"(sel_next[0]), "v"(sel_next[1]));
@@ -2005,9 +2102,14 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       __builtin_amdgcn_sched_barrier(0);
       f2v hs[3];
       float lraw;
-      hand_step_2x5<LOSS>(f2v{zp0, zp1}, o0, o1, hs[0], hs[1], hs[2], lraw, f2v{x[0][0], x[0][1]}, f2v{x[0][2], x[0][3]},
-                          f2v{x[0][4], one[0]}, f2v{x[1][0], x[1][1]}, f2v{x[1][2], x[1][3]}, f2v{x[1][4], one[1]}, ypk[0],
-                          ypk[1], own_m0, ldx4, rec4, Wb[0], cg2);
+      if constexpr (VAR == kWaveLeanPlain)
+        hand_step_2x5_rs<LOSS>(f2v{zp0, zp1}, o0, o1, hgx, hgy, lraw, f2v{x[0][0], x[0][1]}, f2v{x[0][2], x[0][3]},
+                               f2v{x[0][4], one[0]}, f2v{x[1][0], x[1][1]}, f2v{x[1][2], x[1][3]}, f2v{x[1][4], one[1]},
+                               ypk[0], ypk[1], own_m0, ldx4, rec4, Wb[0], cg2);
+      else
+        hand_step_2x5<LOSS>(f2v{zp0, zp1}, o0, o1, hs[0], hs[1], hs[2], lraw, f2v{x[0][0], x[0][1]}, f2v{x[0][2], x[0][3]},
+                            f2v{x[0][4], one[0]}, f2v{x[1][0], x[1][1]}, f2v{x[1][2], x[1][3]}, f2v{x[1][4], one[1]}, ypk[0],
+                            ypk[1], own_m0, ldx4, rec4, Wb[0], cg2);
       *rp = lraw;
       rp += 64;
 #pragma unroll
@@ -2019,23 +2121,18 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       // pads the loads with s_nop
       asm volatile("" ::"v"(o0), "v"(o1));
       __builtin_amdgcn_sched_barrier(0);
-      const float gr[KP + 1] = {hs[0].x, hs[0].y, hs[1].x, hs[1].y, hs[2].x, hs[2].y};
-      if constexpr (VAR == kWaveLeanPlain) {  // train's packed plain SGD: [W[0][0 .. 4], Wb[0]] in pairs
-        float u[KP + 1];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) u[k] = W[0][k];
-        u[KP] = Wb[0];
-#pragma unroll
-        for (int k = 0; k + 1 < KP + 1; k += 2) {
-          const f2v nl = {-lr, k + 1 == KP ? -lr_b : -lr};
-          const f2v r = __builtin_elementwise_fma(nl, f2v{gr[k], gr[k + 1]}, f2v{u[k], u[k + 1]});
-          u[k] = r.x;
-          u[k + 1] = r.y;
-        }
-#pragma unroll
-        for (int k = 0; k < KP; ++k) W[0][k] = u[k];
-        Wb[0] = u[KP];
+      if constexpr (VAR == kWaveLeanPlain) {
+        // train's plain SGD on [W[0][0 .. 4], Wb[0]], each sum read from its lane by the update. The
+        // store and the gathers above stand between the block and the first read of what it wrote
+        // (a DPP read: two instructions at least). Gk is formed where the run ends (hand_run_end).
+        f2v w01 = {W[0][0], W[0][1]}, w23 = {W[0][2], W[0][3]};
+        hand_sgd_bcast(w01, w23, W[0][4], Wb[0], hgx, hgy, nlr, nlr_b);
+        W[0][0] = w01.x;
+        W[0][1] = w01.y;
+        W[0][2] = w23.x;
+        W[0][3] = w23.y;
       } else {  // train's momentum update
+        const float gr[KP + 1] = {hs[0].x, hs[0].y, hs[1].x, hs[1].y, hs[2].x, hs[2].y};
         const bool first = opt_step == 0;
         auto upd = [&](float& w, float& m, float g) {
           float d = fmaf(wd, w, g);
@@ -2049,10 +2146,23 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         upd(Wb[0], Mb[0], gr[KP]);
         Wb[0] = hb ? Wb[0] : 0.f;
         ++opt_step;
-      }
 #pragma unroll
-      for (int k = 0; k < KP; ++k) Gk[0][k] = gr[k];
-      Gbk[0] = gr[KP];
+        for (int k = 0; k < KP; ++k) Gk[0][k] = gr[k];
+        Gbk[0] = gr[KP];
+      }
+    };
+    // Where a run of unchecked groups ends: the last step's gradient from the two registers of its
+    // scattered sums, once (the momentum kernels copied it per step above). A checked group or the tail
+    // behind the run overwrites it as they overwrite every step's.
+    auto hand_run_end = [&]() {
+      if constexpr (VAR == kWaveLeanPlain) {
+        Gk[0][0] = dpp_f<0x150 + kHsBcast[0]>(hgx);
+        Gk[0][1] = dpp_f<0x150 + kHsBcast[1]>(hgx);
+        Gk[0][2] = dpp_f<0x150 + kHsBcast[2]>(hgx);
+        Gk[0][3] = dpp_f<0x150 + kHsBcast[3]>(hgx);
+        Gk[0][4] = dpp_f<0x150 + kHsBcast[4]>(hgy);
+        Gbk[0] = dpp_f<0x150 + kHsBcast[5]>(hgy);
+      }
     };
     done = wave_loop_run(
         sch, n,
@@ -2061,6 +2171,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
           for (int u = 0; u < kNB; ++u) train_hand(buf[u]);
           return true;
         },
+        hand_run_end,
         [&](WaveLoopSchedule& c) {
 #pragma unroll
           for (int u = 0; u < kNB; ++u) {

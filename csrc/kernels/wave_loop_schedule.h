@@ -122,9 +122,12 @@ struct WaveLoopSchedule {
 // checked(s): one group with s.next() and s.slot_done() after every step; one follows every run (a
 //   run of no group included) unless the launch's groups are used up.
 // tail(s, left): the last left < depth steps, no reads, s.slot_done() after each; returns the steps done.
+// run_end(): after a run of at least one group, before anything else runs (what a caller's unchecked
+//   body leaves to be done once per run, not per step).
 // unchecked and checked return false to end the launch after the group. Returns the steps done.
-template <class Unchecked, class Checked, class Tail>
-PTDT_HD inline int wave_loop_run(WaveLoopSchedule& s, int n, Unchecked&& unchecked, Checked&& checked, Tail&& tail) {
+template <class Unchecked, class RunEnd, class Checked, class Tail>
+PTDT_HD inline int wave_loop_run(WaveLoopSchedule& s, int n, Unchecked&& unchecked, RunEnd&& run_end, Checked&& checked,
+                                 Tail&& tail) {
   const int ngroups = n / s.depth;
   int left = ngroups;
   bool go = true;
@@ -137,6 +140,7 @@ PTDT_HD inline int wave_loop_run(WaveLoopSchedule& s, int n, Unchecked&& uncheck
     }
     s.advance(r - k);
     left -= r - k;
+    if (r - k > 0) run_end();
     // A run is maximal: it ends at the launch's last group or where the next group does not fit.
     // The checked group follows the run on one path (not as the other arm of an if / else on r): with
     // the two bodies as siblings the compiler kept their registers apart and copied every live value,
@@ -149,6 +153,11 @@ PTDT_HD inline int wave_loop_run(WaveLoopSchedule& s, int n, Unchecked&& uncheck
   int done = (ngroups - left) * s.depth;
   if (go && done < n) done += tail(s, n - done);
   return done;
+}
+
+template <class Unchecked, class Checked, class Tail>
+PTDT_HD inline int wave_loop_run(WaveLoopSchedule& s, int n, Unchecked&& unchecked, Checked&& checked, Tail&& tail) {
+  return wave_loop_run(s, n, unchecked, []() {}, checked, tail);
 }
 
 // The loop with one group body under a per-group flag, as the lean kernels ran it before the run
