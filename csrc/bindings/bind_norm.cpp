@@ -454,6 +454,36 @@ std::vector<Tensor> conv1x1_bwd_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor 
   return {dx, dw};
 }
 
+bool conv1x1_bwd_tiled_supported_(int64_t K, int64_t N) {
+  return K >= 64 && N >= 64 && K <= 4096 && N <= 4096 && conv1x1_bwd_tiled_supported((int)K, (int)N);
+}
+
+// The same from the tiled kernels (conv1x1_bwd_tiled.hip): any K, N in 64 .. 4096, multiples of 64.
+std::vector<Tensor> conv1x1_bwd_tiled_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor coef) {
+  TORCH_CHECK(g.is_cuda() && y.is_cuda() && x.is_cuda() && w.is_cuda() && coef.is_cuda(),
+              "conv1x1_bwd_tiled: GPU operands");
+  TORCH_CHECK(g.dim() == 2 && y.sizes() == g.sizes() && x.dim() == 2 && w.dim() == 2 && x.size(0) == g.size(0) &&
+                  w.size(0) == g.size(1) && w.size(1) == x.size(1),
+              "conv1x1_bwd_tiled: g, y [M, N], x [M, K], w [N, K]");
+  for (const Tensor* t : {&g, &y, &x, &w})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous(), "conv1x1_bwd_tiled: contiguous bf16 operands");
+  const int64_t M = g.size(0), N = g.size(1), K = x.size(1);
+  TORCH_CHECK(conv1x1_bwd_tiled_supported_(K, N), "conv1x1_bwd_tiled: (K, N) = (", K, ", ", N,
+              ") must be multiples of 64 in 64 .. 4096");
+  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * N,
+              "conv1x1_bwd_tiled: coef [3, N] float");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31), "conv1x1_bwd_tiled: 1 <= M < 2^31");
+  c10::hip::HIPGuard guard(g.device().index());
+  Tensor dx = at::empty({M, K}, x.options());
+  Tensor dw = at::empty({N, K}, w.options());
+  Tensor ws = at::empty({conv1x1_bwd_tiled_ws_floats((int)M, (int)K, (int)N)}, g.options().dtype(at::kFloat));
+  hip_check(conv1x1_bwd_tiled(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), coef.data_ptr<float>(),
+                              dx.data_ptr(), dw.data_ptr(), ws.data_ptr<float>(), (int)M, (int)K, (int)N,
+                              cur_stream(g)),
+            "conv1x1_bwd_tiled");
+  return {dx, dw};
+}
+
 // y = ReLU?(x*scale + shift (+ residual)), per channel (eval-mode BN).
 Tensor bn_apply_(Tensor x, c10::optional<Tensor> residual, Tensor scale, Tensor shift, bool relu) {
   int64_t M;
@@ -532,6 +562,12 @@ void bind_norm(py::module_& m) {
   m.def("bn_bwd_reduce", &bn_bwd_reduce, "BN backward reduce pass only: (g, dweight, dbias, coef[3, C])");
   m.def("conv1x1_bwd", &conv1x1_bwd_, "fused BN-apply + 1x1 conv data and weight gradients (bf16)");
   m.def("conv1x1_bwd_supported", &conv1x1_bwd_supported_);
+  m.def("conv1x1_bwd_tiled", &conv1x1_bwd_tiled_, "the same, K/N-tiled kernels: any K, N % 64 == 0 up to 4096 (bf16)");
+  m.def("conv1x1_bwd_tiled_supported", &conv1x1_bwd_tiled_supported_);
+  m.def("conv1x1_bwd_tiled_splits", [](int64_t M, int64_t K, int64_t N) {
+    const bool ok = M >= 1 && M < (1LL << 31) && conv1x1_bwd_tiled_supported_(K, N);
+    return ok ? conv1x1_bwd_tiled_splits((int)M, (int)K, (int)N) : 0;
+  }, "fp32 weight-gradient partials of conv1x1_bwd_tiled: a function of the shape only");
   m.def("bn_relu", &bn_relu);
   m.def("bn_max_channels", &bn_max_channels, "widest channel count the NHWC BatchNorm kernels take");
   m.def("bn_geometry", [](int64_t M, int64_t C, bool f32) {

@@ -281,6 +281,12 @@ static void bwd_geometry(int M, int K, int N, int* G) {
   bwd_dispatch(K, N, [&](auto k, auto n) { *G = bwd_rows<decltype(k)::value, decltype(n)::value>(M); });
 }
 
+hipError_t conv1x1_bwd_merge(const float* ws, int G, int nk4, void* dw, hipStream_t s) {
+  hipLaunchKernelGGL(conv1x1_bwd_merge_kernel, dim3((nk4 + 63) / 64), dim3(64 * kMergeWaves), 0, s, ws, G, nk4,
+                     static_cast<uint16_t*>(dw));
+  return hipGetLastError();
+}
+
 int64_t conv1x1_bwd_ws_floats(int M, int K, int N) {
   int G;
   bwd_geometry(M, K, N, &G);

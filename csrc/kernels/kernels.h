@@ -686,6 +686,16 @@ bool conv1x1_bwd_supported(int K, int N);
 int64_t conv1x1_bwd_ws_floats(int M, int K, int N);
 hipError_t conv1x1_bwd(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
                        void* dw, float* ws, int M, int K, int N, hipStream_t s);
+// dw [N, K] bf16 = the sum of G fp32 partials ws[G][N K] in a fixed order (nk4 = N K / 4)
+hipError_t conv1x1_bwd_merge(const float* ws, int G, int nk4, void* dw, hipStream_t s);
+// The same backward for any K, N in 64 .. 4096, multiples of 64 (csrc/kernels/conv1x1_bwd_tiled.hip): a
+// tiled data-gradient kernel, a split-M weight-gradient kernel whose splits (a function of the shape
+// only) leave ws[splits][N][K] partials, and conv1x1_bwd_merge. 1 <= M < 2^31.
+bool conv1x1_bwd_tiled_supported(int K, int N);
+int conv1x1_bwd_tiled_splits(int M, int K, int N);
+int64_t conv1x1_bwd_tiled_ws_floats(int M, int K, int N);
+hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
+                             void* dw, float* ws, int M, int K, int N, hipStream_t s);
 // y = ReLU?(x*scale + shift (+ residual)) per channel (eval-mode BN, or any affine epilogue)
 hipError_t bn_apply(const void* x, const void* residual, void* y, int dtype, const float* scale, const float* shift,
                     int64_t M, int C, int relu, hipStream_t s);

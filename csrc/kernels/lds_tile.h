@@ -86,16 +86,22 @@ __device__ __forceinline__ void wg_barrier() {
 // Issue the LDS-DMAs of one ROWS-row tile: elements k0 .. (ROW_BYTES of them) of the global rows
 // row_of(r) (r = tile row; row_of clamps edge rows, which are computed and never stored) of a matrix
 // of E with rows ld elements apart. wid must be wave-uniform (readfirstlane): the LDS base of a DMA
-// is, the hardware adds lane * 16.
-template <int ROWS, int ROW_BYTES, int THREADS, class E, class RowOf>
+// is, the hardware adds lane * 16. col_of(e) maps a 16-B chunk's element offset e from k0 to the offset
+// to read (a tile that sticks out of the matrix re-reads valid columns: conv1x1_bwd_tiled.hip).
+template <int ROWS, int ROW_BYTES, int THREADS, class E, class RowOf, class ColOf>
 __device__ __forceinline__ void stage_rows(const E* __restrict__ src, int64_t ld, int k0, uint8_t* lds_tile, int wid,
-                                           int lane, RowOf row_of) {
+                                           int lane, RowOf row_of, ColOf col_of) {
 #pragma unroll
   for (int i = 0; i < stage_rounds<ROWS, ROW_BYTES, THREADS>(); ++i) {
     const TileChunk s = staged_chunk<ROW_BYTES>(i * THREADS + wid * 64 + lane);
-    const E* g = src + (int64_t)row_of(s.r) * ld + k0 + s.c * (16 / (int)sizeof(E));
+    const E* g = src + (int64_t)row_of(s.r) * ld + k0 + col_of(s.c * (16 / (int)sizeof(E)));
     __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)(lds_tile + (i * THREADS + wid * 64) * 16), 16, 0, 0);
   }
+}
+template <int ROWS, int ROW_BYTES, int THREADS, class E, class RowOf>
+__device__ __forceinline__ void stage_rows(const E* __restrict__ src, int64_t ld, int k0, uint8_t* lds_tile, int wid,
+                                           int lane, RowOf row_of) {
+  stage_rows<ROWS, ROW_BYTES, THREADS>(src, ld, k0, lds_tile, wid, lane, row_of, [](int e) { return e; });
 }
 
 template <class V, int ROW_BYTES>

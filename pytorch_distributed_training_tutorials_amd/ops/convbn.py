@@ -19,10 +19,16 @@ statistics. The BN then runs only its apply pass (``bn_fwd_apply``): the separat
 statistics pass -- a full read of the conv output -- is gone (bf16, batch 128:
 -214 us per ResNet-50 step, profiles/r3_convbn.md).
 
-Backward is unchanged: the BN's native backward, then the convolution's data and
-weight gradients on MIOpen (``aten.convolution_backward``, as autograd would
-call it). Forward numerics: the statistics are those of the stored bf16 output
-(what the separate pass would read), merged in double.
+Backward (``PTDT_CONVBN_BWD``): ``1`` (default) links the BN's backward to the conv's where the
+streaming kernel ``conv1x1_bwd.hip`` has an instance and this module ran the forward: the BN runs
+only its reduce pass and the conv's backward forms ``dY = A g + B y + C`` inside its data- and
+weight-gradient products (:class:`ConvBwdLink`). ``all`` does so for every other shape the K/N-tiled
+kernels of ``conv1x1_bwd_tiled.hip`` take (K, N multiples of 64 up to 4096: ResNet-50's layer2-4),
+whoever ran the forward: where MIOpen's forward wins the timing, it runs inside a small autograd
+Function with the same linked backward. ``0``, and any shape without a kernel: the BN's native
+backward, then the convolution's gradients on MIOpen (``aten.convolution_backward``, as autograd
+would call it). ``PTDT_CONVBN_BWD_SKIP`` keeps single shapes unlinked. Forward numerics: the
+statistics are those of the stored bf16 output (what the separate pass would read), merged in double.
 
 Anything else -- stride 2, eval mode, fp32, NCHW, odd channel counts, CPU --
 takes the unfused ``bn_act(bn, conv(x))``. Where both apply, ``PTDT_CONVBN=auto`` (default)
@@ -48,8 +54,10 @@ _MODE = os.environ.get("PTDT_CONVBN", "auto")  # auto: per-shape timing decides;
 _ENABLED = _MODE not in ("0", "off")
 _STREAM = os.environ.get("PTDT_CONVBN_STREAM", "1") != "0"
 # fused backward (BN apply + 1x1 data and weight gradients, csrc/kernels/conv1x1_bwd.hip) where an
-# instance exists; 0: the BN's full backward, then MIOpen's convolution_backward
+# instance exists; 0: the BN's full backward, then MIOpen's convolution_backward; all: also the tiled
+# kernels (conv1x1_bwd_tiled.hip) for every other shape they take, behind either forward
 _BWD = os.environ.get("PTDT_CONVBN_BWD", "1") != "0"
+_BWD_TILED = os.environ.get("PTDT_CONVBN_BWD", "1") == "all"
 # A/B of single shapes: "KxN,KxN" (input x output channels) keep the unfused backward
 _BWD_SKIP = {tuple(int(v) for v in t.split("x")) for t in os.environ.get("PTDT_CONVBN_BWD_SKIP", "").split(",") if t}
 _CHOICE: dict[tuple, bool] = {}  # (M, K, N, tile) -> fused is faster (PTDT_CONVBN=auto)
@@ -70,10 +78,45 @@ class ConvBwdLink:
     conv's backward then computes dY on the fly inside its data- and weight-gradient GEMMs. None:
     the BN ran its full backward (the conv receives dY itself)."""
 
-    __slots__ = ("coef",)
+    __slots__ = ("coef", "tiled")
 
-    def __init__(self):
+    def __init__(self, tiled: bool = False):
         self.coef = None
+        self.tiled = tiled  # conv1x1_bwd_tiled.hip instead of the streaming instance
+
+
+def _bwd_link(cin: int, cout: int) -> ConvBwdLink | None:
+    """The link for a cin -> cout convolution, or None: no kernel for the shape, or switched off."""
+    if not (_BWD and torch.is_grad_enabled()) or (cin, cout) in _BWD_SKIP:
+        return None
+    if native().conv1x1_bwd_supported(cin, cout):
+        return ConvBwdLink()
+    if _BWD_TILED and native().conv1x1_bwd_tiled_supported(cin, cout):
+        return ConvBwdLink(tiled=True)
+    return None
+
+
+def _conv_backward(ctx, gy, x, w, y2):
+    """(dx, dw) of y = conv1x1(x, w): linked (gy is the BN's masked gradient g, ctx.link holds the
+    coefficients) or plain (gy is dY: MIOpen)."""
+    link = ctx.link
+    if link is not None and link.coef is not None:
+        coef, link.coef = link.coef, None
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        g2 = gy.permute(0, 2, 3, 1).reshape(-1, cout)
+        if not g2.is_contiguous():
+            g2 = g2.contiguous()
+        x2 = x.permute(0, 2, 3, 1).reshape(-1, cin)
+        bwd = native().conv1x1_bwd_tiled if link.tiled else native().conv1x1_bwd
+        dx2, dw2 = bwd(g2, y2, x2, w.reshape(cout, cin), coef)
+        dx = dx2.view(n, h, wd, cin).permute(0, 3, 1, 2) if ctx.needs_input_grad[0] else None
+        dw = dw2.view(cout, cin, 1, 1) if ctx.needs_input_grad[1] else None
+        return dx, dw
+    gy = gy.contiguous(memory_format=torch.channels_last)
+    mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+    dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
+    return dx, dw
 
 
 class _Conv1x1StatsFn(torch.autograd.Function):
@@ -95,24 +138,25 @@ class _Conv1x1StatsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, _gstats):
         x, w, y2 = ctx.saved_tensors
-        link = ctx.link
-        if link is not None and link.coef is not None:  # gy is the BN's masked gradient g (ConvBwdLink)
-            coef, link.coef = link.coef, None
-            n, cin, h, wd = x.shape
-            cout = w.shape[0]
-            g2 = gy.permute(0, 2, 3, 1).reshape(-1, cout)
-            if not g2.is_contiguous():
-                g2 = g2.contiguous()
-            x2 = x.permute(0, 2, 3, 1).reshape(-1, cin)
-            dx2, dw2 = native().conv1x1_bwd(g2, y2, x2, w.reshape(cout, cin), coef)
-            dx = dx2.view(n, h, wd, cin).permute(0, 3, 1, 2) if ctx.needs_input_grad[0] else None
-            dw = dw2.view(cout, cin, 1, 1) if ctx.needs_input_grad[1] else None
-            return dx, dw, *([None] * 10)
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
-        dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                                        mask)
-        return dx, dw, *([None] * 10)
+        return *_conv_backward(ctx, gy, x, w, y2), *([None] * 10)
+
+
+class _Conv1x1LinkedFn(torch.autograd.Function):
+    """y = conv1x1(x, w) on MIOpen (NHWC bf16) with the linked backward (PTDT_CONVBN_BWD=all where
+    MIOpen's forward wins the timing): the backward does not depend on who computed y."""
+
+    @staticmethod
+    def forward(ctx, x, w, link):
+        y = torch.nn.functional.conv2d(x, w).contiguous(memory_format=torch.channels_last)
+        ctx.link = link
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, y = ctx.saved_tensors
+        y2 = y.permute(0, 2, 3, 1).reshape(-1, w.shape[0])
+        return *_conv_backward(ctx, gy, x, w, y2), None
 
 
 def _fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual) -> bool:
@@ -208,7 +252,12 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
     M = x.shape[0] * x.shape[2] * x.shape[3]
     tile = _tile(M, conv.out_channels, conv.in_channels)
     w = cast_weight(conv.weight)
+    cin, cout = conv.in_channels, conv.out_channels
     if not _fused_wins(x, w, tile):
+        clink = _bwd_link(cin, cout) if _BWD_TILED else None
+        if clink is not None:  # MIOpen's forward, the BN's own statistics, the linked backward
+            y = _Conv1x1LinkedFn.apply(x, w, clink)
+            return batch_norm_act(y, bn, residual, relu, link, conv_link=clink)
         from ..models.resnet import bn_act
 
         return bn_act(bn, conv._conv_forward(x, w, None), residual, relu, link)
@@ -217,10 +266,7 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
     need = native().conv1x1_bn_num_tickets(M, conv.out_channels, tile, conv.in_channels)
     if tickets.numel() < need or tickets.device != x.device:
         raise RuntimeError(f"conv_bn_act: BN ticket buffer too small ({tickets.numel()} < {need}) or off-device")
-    cin, cout = conv.in_channels, conv.out_channels
-    clink = None
-    if _BWD and torch.is_grad_enabled() and (cin, cout) not in _BWD_SKIP and native().conv1x1_bwd_supported(cin, cout):
-        clink = ConvBwdLink()
+    clink = _bwd_link(cin, cout)
     y, stats = _Conv1x1StatsFn.apply(x, w, bn.weight, bn.bias, bn.running_mean if track else None,
                                      bn.running_var if track else None, bn.num_batches_tracked if track else None,
                                      float(bn.momentum), float(bn.eps), tickets, tile, clink)

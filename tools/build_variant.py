@@ -34,7 +34,7 @@ def main(argv=None):
     for src in kernels:
         if src.stem in units:
             obj = out_dir / (src.stem + ".o")
-            extra = ["-fno-slp-vectorize"] if src.stem.startswith("linear_wave") else []
+            extra = B.unit_flags(src.stem)
             todo.append([hipcc, *common, *extra, *[f"-D{d}" for d in a.defines], "-c", str(src), "-o", str(obj)])
         else:
             obj = B.BUILD / (src.stem + ".o")
