@@ -343,6 +343,7 @@ def main(argv=None):
             "metric": "ResNet-50 DDP training throughput (whole node)", "value": round(a.steps * a.batch_size * world / el, 1),
             "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(1e3 * el / a.steps, 3), "higher_is_better": True, "scaling": "weak",
+            "peak_mem_MB": round(torch.cuda.max_memory_allocated() / 1e6, 1),
             "dtype": a.dtype, "data": "synthetic ImageNet-shaped (generated on device)",
             "config": {"model": "resnet50", "per_device_batch": a.batch_size, "image": a.image,
                        "parallelism": f"dp{world}", "channels_last": not a.no_channels_last},

@@ -246,6 +246,65 @@ std::vector<Tensor> conv1x1_bn_stats(Tensor x, Tensor w, c10::optional<Tensor> w
   return {y, stats};
 }
 
+// The statistics pass of bn_fwd_train alone (same kernel, same finalise, running statistics updated): stats
+// [4, C], no y. For a consumer that applies scale / shift itself (conv1x1_pre_bn_stats).
+Tensor bn_fwd_stats(Tensor x, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
+                    c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
+                    c10::optional<Tensor> num_batches_tracked, double momentum, double eps,
+                    c10::optional<Tensor> tickets) {
+  return bn_fwd_train(x, weight, bias, running_mean, running_var, num_batches_tracked, c10::nullopt, false, momentum,
+                      eps, tickets, false, /*stats_only=*/true)[1];
+}
+
+bool conv1x1_pre_supported_(int64_t K, int64_t N) {
+  return K >= 64 && N >= 64 && K <= 4096 && N <= 4096 && conv1x1_pre_supported((int)K, (int)N);
+}
+
+int64_t conv1x1_pre_num_tickets_(int64_t M, int64_t K, int64_t N) {
+  const bool ok = M >= 1 && M < (1LL << 31) && conv1x1_pre_supported_(K, N);
+  return ok ? conv1x1_pre_num_tickets((int)M, (int)K, (int)N) : 0;
+}
+
+// 1x1 convolution of a = bf16(max(x * scale + shift, 0)), formed inside the kernel from pre_stats [4, K] (the
+// statistics of the BatchNorm whose input x is: rows 2 and 3), + the training BatchNorm's batch statistics of
+// the output, as conv1x1_bn_stats: returns (y [M, N] bf16, stats [4, N]).
+std::vector<Tensor> conv1x1_pre_bn_stats_(Tensor x, Tensor pre_stats, Tensor w, c10::optional<Tensor> weight,
+                                          c10::optional<Tensor> bias, c10::optional<Tensor> running_mean,
+                                          c10::optional<Tensor> running_var, c10::optional<Tensor> num_batches_tracked,
+                                          double momentum, double eps, Tensor tickets) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && pre_stats.is_cuda() && x.device() == w.device() &&
+                  x.device() == pre_stats.device(),
+              "conv1x1_pre_bn_stats: GPU operands on one device");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "conv1x1_pre_bn_stats: x [M, K], w [N, K]");
+  for (const Tensor* t : {&x, &w})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv1x1_pre_bn_stats: contiguous, 16-B aligned bf16 operands");
+  const int64_t M = x.size(0), N = w.size(0), K = x.size(1);
+  TORCH_CHECK(conv1x1_pre_supported_(K, N), "conv1x1_pre_bn_stats: (K, N) = (", K, ", ", N,
+              ") must be multiples of 64 in 64 .. 4096");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31), "conv1x1_pre_bn_stats: 1 <= M < 2^31");
+  const float* ps = checked_stats(pre_stats, K);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ps) % 16 == 0, "conv1x1_pre_bn_stats: pre_stats not 16-byte aligned");
+  const int64_t need = conv1x1_pre_num_tickets((int)M, (int)K, (int)N);
+  TORCH_CHECK(tickets.is_cuda() && tickets.device() == x.device() && tickets.scalar_type() == at::kInt &&
+                  tickets.is_contiguous() && tickets.numel() >= need,
+              "conv1x1_pre_bn_stats: tickets must be a zeroed int32 tensor of >= ", need, " elements");
+  c10::hip::HIPGuard guard(x.device().index());
+  Tensor y = at::empty({M, N}, x.options());
+  Tensor stats = at::empty({4, N}, x.options().dtype(at::kFloat));
+  Tensor ws = at::empty({conv1x1_pre_ws_floats((int)M, (int)K, (int)N)}, x.options().dtype(at::kFloat));
+  GemmBnEpi e{};
+  e.ws = ws.data_ptr<float>();
+  e.tickets = tickets.data_ptr<int>();
+  fill_bn_params(e.p, (int)N, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps);
+  split_stats(e.p, stats.data_ptr<float>(), N);
+  hip_check(conv1x1_pre_bn_stats(x.data_ptr(), ps + 2 * K, ps + 3 * K, w.data_ptr(), y.data_ptr(), (int)M, (int)K,
+                                 (int)N, e, cur_stream(x)),
+            "conv1x1_pre_bn_stats");
+  return {y, stats};
+}
+
 // The checks, kernel arguments and output tensors of a backward launch; the caller launches, with
 // `guard` still on x's device. reduce_only: g goes out through dres (want_dres is true), dx stays null.
 // with_coef: dwb is [5, C] = dweight, dbias, A, B, C with coef_a/b/c on its last three rows; else
@@ -458,8 +517,11 @@ bool conv1x1_bwd_tiled_supported_(int64_t K, int64_t N) {
   return K >= 64 && N >= 64 && K <= 4096 && N <= 4096 && conv1x1_bwd_tiled_supported((int)K, (int)N);
 }
 
-// The same from the tiled kernels (conv1x1_bwd_tiled.hip): any K, N in 64 .. 4096, multiples of 64.
-std::vector<Tensor> conv1x1_bwd_tiled_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor coef) {
+// The same from the tiled kernels (conv1x1_bwd_tiled.hip): any K, N in 64 .. 4096, multiples of 64. pre
+// ([2, K] f32: scale, shift of the BatchNorm + ReLU between x and the convolution, conv1x1_pre_bn_stats): dw
+// is taken against bf16(max(x * scale + shift, 0)), recomputed; dx is that operand's gradient.
+std::vector<Tensor> conv1x1_bwd_tiled_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor coef,
+                                       c10::optional<Tensor> pre) {
   TORCH_CHECK(g.is_cuda() && y.is_cuda() && x.is_cuda() && w.is_cuda() && coef.is_cuda(),
               "conv1x1_bwd_tiled: GPU operands");
   TORCH_CHECK(g.dim() == 2 && y.sizes() == g.sizes() && x.dim() == 2 && w.dim() == 2 && x.size(0) == g.size(0) &&
@@ -473,11 +535,19 @@ std::vector<Tensor> conv1x1_bwd_tiled_(Tensor g, Tensor y, Tensor x, Tensor w, T
   TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * N,
               "conv1x1_bwd_tiled: coef [3, N] float");
   TORCH_CHECK(M >= 1 && M < (1LL << 31), "conv1x1_bwd_tiled: 1 <= M < 2^31");
+  const float* pp = nullptr;
+  if (has(pre)) {
+    TORCH_CHECK(pre->is_cuda() && pre->device() == g.device() && pre->scalar_type() == at::kFloat &&
+                    pre->is_contiguous() && pre->numel() == 2 * K &&
+                    reinterpret_cast<uintptr_t>(pre->data_ptr()) % 16 == 0,
+                "conv1x1_bwd_tiled: pre [2, K] float, contiguous, 16-byte aligned");
+    pp = pre->data_ptr<float>();
+  }
   c10::hip::HIPGuard guard(g.device().index());
   Tensor dx = at::empty({M, K}, x.options());
   Tensor dw = at::empty({N, K}, w.options());
   Tensor ws = at::empty({conv1x1_bwd_tiled_ws_floats((int)M, (int)K, (int)N)}, g.options().dtype(at::kFloat));
-  hip_check(conv1x1_bwd_tiled(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), coef.data_ptr<float>(),
+  hip_check(conv1x1_bwd_tiled(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), coef.data_ptr<float>(), pp,
                               dx.data_ptr(), dw.data_ptr(), ws.data_ptr<float>(), (int)M, (int)K, (int)N,
                               cur_stream(g)),
             "conv1x1_bwd_tiled");
@@ -562,7 +632,18 @@ void bind_norm(py::module_& m) {
   m.def("bn_bwd_reduce", &bn_bwd_reduce, "BN backward reduce pass only: (g, dweight, dbias, coef[3, C])");
   m.def("conv1x1_bwd", &conv1x1_bwd_, "fused BN-apply + 1x1 conv data and weight gradients (bf16)");
   m.def("conv1x1_bwd_supported", &conv1x1_bwd_supported_);
-  m.def("conv1x1_bwd_tiled", &conv1x1_bwd_tiled_, "the same, K/N-tiled kernels: any K, N % 64 == 0 up to 4096 (bf16)");
+  m.def("conv1x1_bwd_tiled", &conv1x1_bwd_tiled_, "the same, K/N-tiled kernels: any K, N % 64 == 0 up to 4096 (bf16)",
+        py::arg("g"), py::arg("y"), py::arg("x"), py::arg("w"), py::arg("coef"), py::arg("pre") = py::none());
+  m.def("bn_fwd_stats", &bn_fwd_stats, "bn_fwd_train's statistics pass alone: stats[4, C], running statistics updated",
+        py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"), py::arg("tickets") = py::none());
+  m.def("conv1x1_pre_bn_stats", &conv1x1_pre_bn_stats_,
+        "1x1 conv of ReLU(BN(x)) formed on the operand path + BN statistics of the output: (y, stats[4, N])",
+        py::arg("x"), py::arg("pre_stats"), py::arg("w"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"),
+        py::arg("tickets"));
+  m.def("conv1x1_pre_supported", &conv1x1_pre_supported_, py::arg("K"), py::arg("N"));
+  m.def("conv1x1_pre_num_tickets", &conv1x1_pre_num_tickets_, py::arg("M"), py::arg("K"), py::arg("N"));
   m.def("conv1x1_bwd_tiled_supported", &conv1x1_bwd_tiled_supported_);
   m.def("conv1x1_bwd_tiled_splits", [](int64_t M, int64_t K, int64_t N) {
     const bool ok = M >= 1 && M < (1LL << 31) && conv1x1_bwd_tiled_supported_(K, N);

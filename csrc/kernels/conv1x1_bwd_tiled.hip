@@ -5,6 +5,7 @@
 //   dY[m, n] = fma(A[n], g[m, n], fma(B[n], y[m, n], C[n]))   rounded to bf16, never stored; 0 for m >= M
 //   dX[M, K] = dY . W                                          fp32 accumulate, bf16 out
 //   dW[N, K] = dY^T . X                                        fp32 accumulate, fixed-order merge, bf16 out
+//              (pre given: dY^T . a, a = bf16(max(fmaf(X, scale, shift), 0)) recomputed, conv1x1_pre.hip)
 //
 // Two tiled MFMA kernels (v_mfma_f32_16x16x32_bf16, 4 waves as 2 x 2 of 64 x 64, 2 workgroups per CU),
 // each forming dY in its operand path, then conv1x1_bwd.hip's merge kernel:
@@ -96,6 +97,18 @@ __device__ __forceinline__ bf16x8_t read_tr(const uint8_t* img, int rb, int chun
   const s16x4_t hi =
       __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + tile_off<256>(rb + 4, chunk) + 8 * half));
   return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// The fragment of the recomputed operand a = bf16(max(fmaf(x, scale, shift), 0)) (conv1x1_pre.hip) from a
+// read_tr fragment of x: one channel (this lane's scale / shift) over 8 rows.
+__device__ __forceinline__ bf16x8_t pre_frag(bf16x8_t xf, float sc, float sf) {
+  const u32x4_t xv = __builtin_bit_cast(u32x4_t, xf);
+  u32x4_t pk;
+#pragma unroll
+  for (int h = 0; h < 4; ++h)
+    pk[h] = pack_bf16x2(fmaxf(fmaf(__uint_as_float(xv[h] << 16), sc, sf), 0.f),
+                        fmaxf(fmaf(__uint_as_float(xv[h] & 0xffff0000u), sc, sf), 0.f));
+  return __builtin_bit_cast(bf16x8_t, pk);
 }
 
 // ---- data gradient: dX[m0 .. +127][k0 .. +127], block = (row tile) * ktn + (k tile)
@@ -194,10 +207,15 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dx_kernel(
 }
 
 // ---- weight gradient: partial of dW[n0 .. +127][k0 .. +127] over the row blocks of split s,
-// block = s * tiles + (n tile) * ktn + (k tile)
+// block = s * tiles + (n tile) * ktn + (k tile). PRE: X is the input of a BatchNorm + ReLU (pre = its
+// scale[K], shift[K]) and the product takes a = bf16(max(fmaf(x, scale, shift), 0)), formed on the X
+// fragments: a lane's fragment of k tile t is channel 16 t + fr over 8 rows, so its 4 + 4 coefficients
+// serve the whole launch.
+template <bool PRE>
 __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dw_kernel(
     const uint16_t* __restrict__ G, const uint16_t* __restrict__ Y, const uint16_t* __restrict__ X,
-    const float* __restrict__ coef, float* __restrict__ ws, int M, int K, int N, int ktn, int tiles, int S) {
+    const float* __restrict__ coef, const float* __restrict__ pre, float* __restrict__ ws, int M, int K, int N,
+    int ktn, int tiles, int S) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint8_t* const dyb = smem;            // 2 x [64 m][128 n]
   uint8_t* const xb = smem + 2 * kImg;  // 2 x [64 m][128 k]
@@ -233,6 +251,16 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dw_kernel(
     });
   };
 
+  float psc[4], psf[4];
+  if constexpr (PRE) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int k = k0 + 64 * wk + 16 * t + fr;
+      psc[t] = pre[k < K ? k : K - 1];  // a tile past K: valid coefficients, nothing stored
+      psf[t] = pre[K + (k < K ? k : K - 1)];
+    }
+  }
+
   f32x4_t acc[4][4];  // [n tile a][k tile t]
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -265,7 +293,10 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dw_kernel(
 #pragma unroll
       for (int a = 0; a < 4; ++a) af[a] = read_tr(dyt, rb, 8 * wn + 2 * a + (tp >> 1), tp & 1);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) bfv[t] = read_tr(xt, rb, 8 * wk + 2 * t + (tp >> 1), tp & 1);
+      for (int t = 0; t < 4; ++t) {
+        bfv[t] = read_tr(xt, rb, 8 * wk + 2 * t + (tp >> 1), tp & 1);
+        if constexpr (PRE) bfv[t] = pre_frag(bfv[t], psc[t], psf[t]);
+      }
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -289,6 +320,21 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dw_kernel(
 
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+template <bool PRE>
+hipError_t launch_dw(const void* g, const void* y, const void* x, const float* coef, const float* pre, float* ws, int M,
+                     int K, int N, int ktn, int tiles, int S, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    PTDT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bwd_tiled_dw_kernel<PRE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+    attr = true;
+  }
+  hipLaunchKernelGGL(conv1x1_bwd_tiled_dw_kernel<PRE>, dim3((unsigned)(S * tiles)), dim3(kThreads), kLds, s,
+                     static_cast<const uint16_t*>(g), static_cast<const uint16_t*>(y),
+                     static_cast<const uint16_t*>(x), coef, pre, ws, M, K, N, ktn, tiles, S);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 bool conv1x1_bwd_tiled_supported(int K, int N) {
@@ -308,20 +354,17 @@ int64_t conv1x1_bwd_tiled_ws_floats(int M, int K, int N) {
   return (int64_t)conv1x1_bwd_tiled_splits(M, K, N) * N * K;
 }
 
-hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
-                             void* dw, float* ws, int M, int K, int N, hipStream_t s) {
+hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const void* w, const float* coef,
+                             const float* pre, void* dx, void* dw, float* ws, int M, int K, int N, hipStream_t s) {
   if (M <= 0 || ws == nullptr || !conv1x1_bwd_tiled_supported(K, N)) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x) |
        reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dw) |
-       reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(coef)) & 15)
+       reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(pre)) & 15)
     return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bwd_tiled_dx_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bwd_tiled_dw_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess)
-      return hipErrorInvalidValue;
+    PTDT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bwd_tiled_dx_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
     attr = true;
   }
   const int ktn = ceil_div(K, kTC), tiles = ceil_div(N, kTC) * ktn;
@@ -330,13 +373,9 @@ hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const 
   hipLaunchKernelGGL(conv1x1_bwd_tiled_dx_kernel, dim3((unsigned)(mt * ktn)), dim3(kThreads), kLds, s,
                      static_cast<const uint16_t*>(g), static_cast<const uint16_t*>(y),
                      static_cast<const uint16_t*>(w), coef, static_cast<uint16_t*>(dx), M, K, N, ktn);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(conv1x1_bwd_tiled_dw_kernel, dim3((unsigned)(S * tiles)), dim3(kThreads), kLds, s,
-                     static_cast<const uint16_t*>(g), static_cast<const uint16_t*>(y),
-                     static_cast<const uint16_t*>(x), coef, ws, M, K, N, ktn, tiles, S);
-  err = hipGetLastError();
-  if (err != hipSuccess) return err;
+  PTDT_HIP_CHECK(hipGetLastError());
+  PTDT_HIP_CHECK(pre ? launch_dw<true>(g, y, x, coef, pre, ws, M, K, N, ktn, tiles, S, s)
+                     : launch_dw<false>(g, y, x, coef, pre, ws, M, K, N, ktn, tiles, S, s));
   return conv1x1_bwd_merge(ws, S, N * K / 4, dw, s);
 }
 

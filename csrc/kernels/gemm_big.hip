@@ -27,6 +27,7 @@
 //   * edges: rows/cols past M/N read a clamped (valid) row and are not stored;
 //     K must be a multiple of 64 (host checks), bases 16-B aligned.
 #include "bn_finish.h"
+#include "bn_merge.h"
 #include "common.h"
 #include "handoff.h"
 #include "kernels.h"
@@ -301,49 +302,6 @@ __global__ void __launch_bounds__(T::NT) gemm_bf16_lds_kernel(BigGemmArgs g, int
 //      reads), updates running_mean / running_var (unbiased) and num_batches_tracked.
 // Deterministic (fixed merge order whatever the arrival order) and robust for |mean| >> std
 // (centred partials). Tickets are re-armed by their last arriver for the next launch.
-// (n, S, Q) <- (n, S, Q) merged with (np, Sp, Qp): S = sum, Q = sum of squares about the mean
-__device__ __forceinline__ void chan_merge(double& n, double& S, double& Q, double np, double Sp, double Qp) {
-  if (np <= 0.0) return;
-  if (n <= 0.0) {
-    n = np, S = Sp, Q = Qp;
-    return;
-  }
-  const double d = Sp / np - S / n;
-  Q += Qp + d * d * n * np / (n + np);
-  S += Sp;
-  n += np;
-}
-
-// Merge partials [p0, p1) (row counts from rows_of(p)) of this tile's BN columns; the NT/BN thread
-// groups take interleaved partials and are merged in group order through LDS. Result (n, S, Q)
-// valid in threads t < BN.
-template <class T, class RowsOf>
-__device__ __forceinline__ void merge_range(const float* wsS, const float* wsQ, int N, int n0, int p0, int p1,
-                                            RowsOf rows_of, double* sh, double& n, double& S, double& Q) {
-  constexpr int PARTS = T::NT / T::BN;
-  const int tid = threadIdx.x, col = tid % T::BN, part = tid / T::BN;
-  const int c = n0 + col;
-  n = S = Q = 0.0;
-  if (c < N) {
-    for (int p = p0 + part; p < p1; p += PARTS)
-      chan_merge(n, S, Q, (double)rows_of(p), (double)ld_sc1(wsS + (int64_t)p * N + c),
-                 (double)ld_sc1(wsQ + (int64_t)p * N + c));
-  }
-  __syncthreads();  // LDS scratch free
-  if (part > 0) {
-    sh[(part * 3 + 0) * T::BN + col] = n;
-    sh[(part * 3 + 1) * T::BN + col] = S;
-    sh[(part * 3 + 2) * T::BN + col] = Q;
-  }
-  __syncthreads();
-  if (part == 0) {
-#pragma unroll
-    for (int q = 1; q < PARTS; ++q)
-      chan_merge(n, S, Q, sh[(q * 3 + 0) * T::BN + col], sh[(q * 3 + 1) * T::BN + col],
-                 sh[(q * 3 + 2) * T::BN + col]);
-  }
-}
-
 template <class T, int SCHED>
 __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, GemmBnEpi e, int tm, int tn) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -423,7 +381,7 @@ __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, Gem
   if (!last_arrival(e.tickets + gi * tn + bn, g_count, flag)) return;
   double n, S, Q;
   auto wave_rows = [&](int p) { return max(0, min(g.M - (p / T::WM) * T::BM - (p % T::WM) * WROWS, WROWS)); };
-  merge_range<T>(wsS, wsQ, N, n0, g_first * T::WM, (g_first + g_count) * T::WM, wave_rows, sh, n, S, Q);
+  merge_range<T::NT, T::BN>(wsS, wsQ, N, n0, g_first * T::WM, (g_first + g_count) * T::WM, wave_rows, sh, n, S, Q);
   float* gS = e.ws + (int64_t)2 * P * N;
   float* gQ = gS + (int64_t)ng * N;
   {
@@ -438,7 +396,7 @@ __global__ void __launch_bounds__(T::NT) gemm_bn_stats_kernel(BigGemmArgs g, Gem
   if (!last_arrival(e.tickets + ng * tn + bn, ng, flag)) return;
   const int64_t grows = (int64_t)G * T::BM;
   auto group_rows = [&](int p) { return (int)max((int64_t)0, min((int64_t)g.M - p * grows, grows)); };
-  merge_range<T>(gS, gQ, N, n0, 0, ng, group_rows, sh, n, S, Q);
+  merge_range<T::NT, T::BN>(gS, gQ, N, n0, 0, ng, group_rows, sh, n, S, Q);
   const int c = n0 + tid;
   if (tid < T::BN && c < N) {
     const double Md = (double)g.M;

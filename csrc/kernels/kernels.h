@@ -694,8 +694,19 @@ hipError_t conv1x1_bwd_merge(const float* ws, int G, int nk4, void* dw, hipStrea
 bool conv1x1_bwd_tiled_supported(int K, int N);
 int conv1x1_bwd_tiled_splits(int M, int K, int N);
 int64_t conv1x1_bwd_tiled_ws_floats(int M, int K, int N);
-hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
-                             void* dw, float* ws, int M, int K, int N, hipStream_t s);
+// pre (optional, [2, K] scale / shift of the BatchNorm that produced x): the weight gradient multiplies by
+// a = bf16(max(fmaf(x, scale, shift), 0)) instead of x (conv1x1_pre.hip's operand); dx is then a's gradient.
+hipError_t conv1x1_bwd_tiled(const void* g, const void* y, const void* x, const void* w, const float* coef,
+                             const float* pre, void* dx, void* dw, float* ws, int M, int K, int N, hipStream_t s);
+// 1x1 convolution on a = bf16(max(fmaf(x, scale, shift), 0)) formed on the operand path, never stored, plus the
+// batch statistics of its own bf16 output as gemm_bn_stats (csrc/kernels/conv1x1_pre.hip): x [M, K], w [N, K],
+// y [M, N] bf16, scale / shift [K] f32 (16-B aligned). K, N as conv1x1_bwd_tiled_supported; 1 <= M < 2^31.
+// e.ws: conv1x1_pre_ws_floats floats; e.tickets: conv1x1_pre_num_tickets zeroed ints (re-armed).
+bool conv1x1_pre_supported(int K, int N);
+int64_t conv1x1_pre_ws_floats(int M, int K, int N);
+int64_t conv1x1_pre_num_tickets(int M, int K, int N);
+hipError_t conv1x1_pre_bn_stats(const void* x, const float* scale, const float* shift, const void* w, void* y, int M,
+                                int K, int N, GemmBnEpi e, hipStream_t s);
 // y = ReLU?(x*scale + shift (+ residual)) per channel (eval-mode BN, or any affine epilogue)
 hipError_t bn_apply(const void* x, const void* residual, void* y, int dtype, const float* scale, const float* shift,
                     int64_t M, int C, int relu, hipStream_t s);

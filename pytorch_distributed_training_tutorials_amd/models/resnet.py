@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.conv import Conv2d
+from ..ops import convbn
 from ..ops.convbn import conv_bn_act
 from ..ops.linear import Linear
 from ..ops.norm import BatchNorm2d, MaxPool2d, bn_relu_maxpool, grad_link
@@ -77,6 +78,9 @@ class Bottleneck(nn.Module):
         identity = x if self.downsample is None else self._down(grad_link(x))
         # 1x1 convs: the BN statistics come from the GEMM epilogue (ops.convbn) where it applies
         out = conv_bn_act(self.conv1, self.bn1, x, relu=True)
+        if convbn._PRE:  # bn2's apply + ReLU run inside conv3's operand loads (PTDT_CONVBN_PRE, ops.convbn)
+            return conv_bn_act(self.conv3, self.bn3, self.conv2(out), residual=identity, relu=True,
+                               link=self.downsample is None, pre_bn=self.bn2)
         out = bn_act(self.bn2, self.conv2(out), relu=True)
         # identity shortcut: the residual gradient goes straight into the producing BN's backward
         return conv_bn_act(self.conv3, self.bn3, out, residual=identity, relu=True, link=self.downsample is None)

@@ -30,6 +30,14 @@ backward, then the convolution's gradients on MIOpen (``aten.convolution_backwar
 would call it). ``PTDT_CONVBN_BWD_SKIP`` keeps single shapes unlinked. Forward numerics: the
 statistics are those of the stored bf16 output (what the separate pass would read), merged in double.
 
+Input BatchNorm (``PTDT_CONVBN_PRE=1``, default 0): ``conv_bn_act(..., pre_bn=bn2)`` takes the RAW input of
+``pre_bn`` and computes ``bn(conv(ReLU(pre_bn(x))))`` without ``pre_bn``'s apply pass: its statistics pass runs
+alone (``bn_fwd_stats``) and ``conv1x1_pre.hip`` forms ``bf16(max(x * scale + shift, 0))`` on its operand path,
+with the output's statistics in its epilogue as above. The backward is the tiled link, whose weight-gradient
+kernel recomputes the same operand from ``x`` (``pre=``), then ``pre_bn``'s own backward: the normalised
+activation is neither written, re-read nor saved (ResNet-50's conv2 -> bn2 -> ReLU -> conv3).
+``PTDT_CONVBN_PRE_SKIP=KxN,...`` keeps single shapes on the composed path.
+
 Anything else -- stride 2, eval mode, fp32, NCHW, odd channel counts, CPU --
 takes the unfused ``bn_act(bn, conv(x))``. Where both apply, ``PTDT_CONVBN=auto`` (default)
 times the two once per shape on the live operands and keeps the faster (MIOpen's 1x1
@@ -48,7 +56,7 @@ import torch.nn as nn
 
 from .._ext import native
 from .conv import cast_weight
-from .norm import BatchNorm2d, batch_norm_act, synchronizing
+from .norm import BatchNorm2d, _like, _rows_layout_ok, _tickets_of, batch_norm_act, synchronizing
 
 _MODE = os.environ.get("PTDT_CONVBN", "auto")  # auto: per-shape timing decides; on / 1: always; off / 0: never
 _ENABLED = _MODE not in ("0", "off")
@@ -60,6 +68,9 @@ _BWD = os.environ.get("PTDT_CONVBN_BWD", "1") != "0"
 _BWD_TILED = os.environ.get("PTDT_CONVBN_BWD", "1") == "all"
 # A/B of single shapes: "KxN,KxN" (input x output channels) keep the unfused backward
 _BWD_SKIP = {tuple(int(v) for v in t.split("x")) for t in os.environ.get("PTDT_CONVBN_BWD_SKIP", "").split(",") if t}
+# the input BN's apply + ReLU inside the 1x1 conv's operand loads (csrc/kernels/conv1x1_pre.hip); no timing
+_PRE = os.environ.get("PTDT_CONVBN_PRE", "0") == "1"
+_PRE_SKIP = {tuple(int(v) for v in t.split("x")) for t in os.environ.get("PTDT_CONVBN_PRE_SKIP", "").split(",") if t}
 _CHOICE: dict[tuple, bool] = {}  # (M, K, N, tile) -> fused is faster (PTDT_CONVBN=auto)
 
 
@@ -159,6 +170,70 @@ class _Conv1x1LinkedFn(torch.autograd.Function):
         return *_conv_backward(ctx, gy, x, w, y2), None
 
 
+class _PreConv1x1StatsFn(torch.autograd.Function):
+    """y = conv1x1(ReLU(pre_bn(x)), w) with pre_bn's training statistics, and the [4, Cout] BN statistics
+    of y (non-differentiable); the normalised activation exists only inside the kernels. Backward: the
+    tiled link (gy is the consuming BN's masked gradient g), then pre_bn's backward with its ReLU mask
+    recomputed from x."""
+
+    @staticmethod
+    def forward(ctx, x, pre_weight, pre_bias, pre_rm, pre_rv, pre_nbt, pre_momentum: float, pre_eps: float,
+                pre_tickets, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum: float, eps: float,
+                tickets, link):
+        C = native()
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        pstats = C.bn_fwd_stats(x, pre_weight, pre_bias, pre_rm, pre_rv, pre_nbt, pre_momentum, pre_eps, pre_tickets)
+        x2 = x.permute(0, 2, 3, 1).reshape(n * h * wd, cin)  # channels_last storage: a view
+        y2, stats = C.conv1x1_pre_bn_stats(x2, pstats, w.reshape(cout, cin), bn_weight, bn_bias, running_mean,
+                                           running_var, nbt, momentum, eps, tickets)
+        ctx.link = link
+        ctx.pre_tickets = pre_tickets
+        ctx.params = (pre_weight, pre_bias)
+        ctx.save_for_backward(x, pre_weight, w, pstats, y2)
+        ctx.mark_non_differentiable(stats)
+        return y2.view(n, h, wd, cout).permute(0, 3, 1, 2), stats
+
+    @staticmethod
+    def backward(ctx, gy, _gstats):
+        x, pre_weight, w, pstats, y2 = ctx.saved_tensors
+        link = ctx.link
+        if link.coef is None:
+            raise RuntimeError("conv_bn_act(pre_bn=): the consuming BN's linked backward did not run")
+        coef, link.coef = link.coef, None
+        C = native()
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        g2 = gy.permute(0, 2, 3, 1).reshape(-1, cout)
+        if not g2.is_contiguous():
+            g2 = g2.contiguous()
+        x2 = x.permute(0, 2, 3, 1).reshape(-1, cin)
+        da2, dw2 = C.conv1x1_bwd_tiled(g2, y2, x2, w.reshape(cout, cin), coef, pstats[2:4])
+        da = _like(da2.view(n, h, wd, cin).permute(0, 3, 1, 2), x)  # the gradient of ReLU(pre_bn(x))
+        want_dw = pre_weight is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        sinks = [None, None]
+        if want_dw:  # DDP grad sinks, as ops/norm.py's _bwd_inputs
+            for k, p in enumerate(ctx.params):
+                if p is not None and p.grad is None and getattr(p, "_ptdt_grad_sink", None) is not None:
+                    sinks[k] = p._ptdt_grad_sink()
+        dx, dpw, dpb, _ = C.bn_bwd(da, x, None, pre_weight, pstats, True, False, want_dw, ctx.pre_tickets, sinks[0],
+                                   sinks[1], None, None)
+        return (dx if ctx.needs_input_grad[0] else None, dpw if want_dw else None, dpb if want_dw else None,
+                *([None] * 6), dw2.view(cout, cin, 1, 1) if ctx.needs_input_grad[9] else None, *([None] * 9))
+
+
+def _pre_fusable(conv: nn.Conv2d, pre_bn: nn.Module, x: torch.Tensor) -> bool:
+    """conv_bn_act(pre_bn=) on top of _fusable(conv, bn, x, residual): a local training BatchNorm2d over the
+    native layout, grad mode (the fusion's point is the backward's saved activation), a shape with a kernel."""
+    if not (_PRE and torch.is_grad_enabled() and isinstance(pre_bn, BatchNorm2d) and pre_bn.training
+            and pre_bn.momentum is not None and not synchronizing(pre_bn)):
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    if pre_bn.num_features != cin or not _rows_layout_ok(x) or (cin, cout) in _PRE_SKIP:
+        return False
+    return native().conv1x1_pre_supported(cin, cout)
+
+
 def _fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual) -> bool:
     if not (_ENABLED and isinstance(bn, BatchNorm2d) and bn.training and bn.momentum is not None):
         return False
@@ -242,9 +317,31 @@ def _fused_wins(x: torch.Tensor, w: torch.Tensor, tile: int) -> bool:
 
 
 def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch.Tensor | None = None,
-                relu: bool = False, link: bool = False) -> torch.Tensor:
+                relu: bool = False, link: bool = False, pre_bn: nn.Module | None = None) -> torch.Tensor:
     """``ReLU?(bn(conv(x)) + residual)``; a stride-1 1x1 ``conv`` feeding an ops.norm.BatchNorm2d in
-    training under bf16 autocast computes the BN statistics in its GEMM epilogue."""
+    training under bf16 autocast computes the BN statistics in its GEMM epilogue. ``pre_bn``: ``x`` is the raw
+    input of that BatchNorm and ``conv`` takes ``ReLU(pre_bn(x))``, applied inside the convolution's kernels
+    where PTDT_CONVBN_PRE allows (module docstring), else composed."""
+    if pre_bn is not None:
+        if not (_fusable(conv, bn, x, residual) and _pre_fusable(conv, pre_bn, x)):
+            from ..models.resnet import bn_act
+
+            return conv_bn_act(conv, bn, bn_act(pre_bn, x, relu=True), residual, relu, link)
+        M = x.shape[0] * x.shape[2] * x.shape[3]
+        cin, cout = conv.in_channels, conv.out_channels
+        tickets = bn._gemm_tickets
+        need = native().conv1x1_pre_num_tickets(M, cin, cout)
+        if tickets.numel() < need or tickets.device != x.device:
+            raise RuntimeError(f"conv_bn_act: BN ticket buffer too small ({tickets.numel()} < {need}) or off-device")
+        clink = ConvBwdLink(tiled=True)
+        ptrack, track = pre_bn.track_running_stats, bn.track_running_stats
+        y, stats = _PreConv1x1StatsFn.apply(
+            x, pre_bn.weight, pre_bn.bias, pre_bn.running_mean if ptrack else None,
+            pre_bn.running_var if ptrack else None, pre_bn.num_batches_tracked if ptrack else None,
+            float(pre_bn.momentum), float(pre_bn.eps), _tickets_of(pre_bn, x), cast_weight(conv.weight), bn.weight,
+            bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+            bn.num_batches_tracked if track else None, float(bn.momentum), float(bn.eps), tickets, clink)
+        return batch_norm_act(y, bn, residual, relu, link, stats=stats, conv_link=clink)
     if not _fusable(conv, bn, x, residual):
         from ..models.resnet import bn_act
 
