@@ -305,6 +305,55 @@ std::vector<Tensor> conv1x1_pre_bn_stats_(Tensor x, Tensor pre_stats, Tensor w, 
   return {y, stats};
 }
 
+bool conv3x3_bn_supported_(int64_t Cin, int64_t Cout) {
+  return Cin >= 64 && Cout >= 64 && Cin <= 1024 && Cout <= 1024 && conv3x3_bn_supported((int)Cin, (int)Cout);
+}
+
+int64_t conv3x3_bn_num_tickets_(int64_t M, int64_t Cin, int64_t Cout, int64_t tile) {
+  const bool ok = M >= 1 && M < (1LL << 31) && conv3x3_bn_supported_(Cin, Cout) &&
+                  (tile == 0 || tile == 64 || tile == 128);
+  return ok ? conv3x3_bn_num_tickets((int)M, (int)Cin, (int)Cout, (int)tile) : 0;
+}
+
+// 3x3 convolution (stride 1, padding 1, no bias) of a channels_last bf16 activation + the training BatchNorm's
+// batch statistics of the output, as conv1x1_bn_stats: x [N, Cin, H, W] and w [Cout, Cin, 3, 3] channels_last;
+// returns (y [N, Cout, H, W] bf16 channels_last, stats [4, Cout]). tile: the kernel's channel tile (0: by shape).
+std::vector<Tensor> conv3x3_bn_stats_(Tensor x, Tensor w, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
+                                      c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
+                                      c10::optional<Tensor> num_batches_tracked, double momentum, double eps,
+                                      Tensor tickets, int64_t tile) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.device() == w.device(), "conv3x3_bn_stats: GPU operands on one device");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && x.size(1) == w.size(1),
+              "conv3x3_bn_stats: x [N, Cin, H, W], w [Cout, Cin, 3, 3]");
+  for (const Tensor* t : {&x, &w})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv3x3_bn_stats: channels_last-contiguous, 16-B aligned bf16 operands");
+  const int64_t B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = w.size(0);
+  const int64_t M = B * H * W;
+  TORCH_CHECK(conv3x3_bn_supported_(Cin, Cout), "conv3x3_bn_stats: (Cin, Cout) = (", Cin, ", ", Cout,
+              ") must be multiples of 64 in 64 .. 1024");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31), "conv3x3_bn_stats: 1 <= N H W < 2^31");
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128, "conv3x3_bn_stats: tile 0 (by shape), 64 or 128");
+  const int64_t need = conv3x3_bn_num_tickets((int)M, (int)Cin, (int)Cout, (int)tile);
+  TORCH_CHECK(tickets.is_cuda() && tickets.device() == x.device() && tickets.scalar_type() == at::kInt &&
+                  tickets.is_contiguous() && tickets.numel() >= need,
+              "conv3x3_bn_stats: tickets must be a zeroed int32 tensor of >= ", need, " elements");
+  c10::hip::HIPGuard guard(x.device().index());
+  Tensor y = at::empty({B, Cout, H, W}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor stats = at::empty({4, Cout}, x.options().dtype(at::kFloat));
+  Tensor ws = at::empty({conv3x3_bn_ws_floats((int)M, (int)Cin, (int)Cout, (int)tile)}, x.options().dtype(at::kFloat));
+  GemmBnEpi e{};
+  e.ws = ws.data_ptr<float>();
+  e.tickets = tickets.data_ptr<int>();
+  fill_bn_params(e.p, (int)Cout, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps);
+  split_stats(e.p, stats.data_ptr<float>(), Cout);
+  hip_check(conv3x3_bn_stats(x.data_ptr(), w.data_ptr(), y.data_ptr(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout, e,
+                             cur_stream(x), (int)tile),
+            "conv3x3_bn_stats");
+  return {y, stats};
+}
+
 // The checks, kernel arguments and output tensors of a backward launch; the caller launches, with
 // `guard` still on x's device. reduce_only: g goes out through dres (want_dres is true), dx stays null.
 // with_coef: dwb is [5, C] = dweight, dbias, A, B, C with coef_a/b/c on its last three rows; else
@@ -644,6 +693,14 @@ void bind_norm(py::module_& m) {
         py::arg("tickets"));
   m.def("conv1x1_pre_supported", &conv1x1_pre_supported_, py::arg("K"), py::arg("N"));
   m.def("conv1x1_pre_num_tickets", &conv1x1_pre_num_tickets_, py::arg("M"), py::arg("K"), py::arg("N"));
+  m.def("conv3x3_bn_stats", &conv3x3_bn_stats_,
+        "3x3 conv (stride 1, padding 1, NHWC bf16 implicit GEMM) + BN statistics of the output: (y, stats[4, Cout])",
+        py::arg("x"), py::arg("w"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"),
+        py::arg("tickets"), py::arg("tile") = 0);
+  m.def("conv3x3_bn_supported", &conv3x3_bn_supported_, py::arg("Cin"), py::arg("Cout"));
+  m.def("conv3x3_bn_num_tickets", &conv3x3_bn_num_tickets_, py::arg("M"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("tile") = 0);
   m.def("conv1x1_bwd_tiled_supported", &conv1x1_bwd_tiled_supported_);
   m.def("conv1x1_bwd_tiled_splits", [](int64_t M, int64_t K, int64_t N) {
     const bool ok = M >= 1 && M < (1LL << 31) && conv1x1_bwd_tiled_supported_(K, N);

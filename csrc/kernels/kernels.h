@@ -707,6 +707,16 @@ int64_t conv1x1_pre_ws_floats(int M, int K, int N);
 int64_t conv1x1_pre_num_tickets(int M, int K, int N);
 hipError_t conv1x1_pre_bn_stats(const void* x, const float* scale, const float* shift, const void* w, void* y, int M,
                                 int K, int N, GemmBnEpi e, hipStream_t s);
+// 3x3 convolution, stride 1, padding 1, as an implicit GEMM over NHWC bf16, plus the batch statistics of its own
+// bf16 output as gemm_bn_stats (csrc/kernels/conv3x3_bn.hip): x [N, H, W, Cin], w [Cout, 3, 3, Cin],
+// y [N, H, W, Cout], all 16-B aligned. Cin, Cout multiples of 64 in 64 .. 1024; 1 <= M = N H W < 2^31.
+// e.ws: conv3x3_bn_ws_floats floats; e.tickets: conv3x3_bn_num_tickets zeroed ints (re-armed). tile: the
+// channel tile, 0 (chosen from the shape), 64 or 128; the same value goes to all three sizing / launch calls.
+bool conv3x3_bn_supported(int Cin, int Cout);
+int64_t conv3x3_bn_ws_floats(int M, int Cin, int Cout, int tile = 0);
+int64_t conv3x3_bn_num_tickets(int M, int Cin, int Cout, int tile = 0);
+hipError_t conv3x3_bn_stats(const void* x, const void* w, void* y, int N, int H, int W, int Cin, int Cout,
+                            GemmBnEpi e, hipStream_t s, int tile = 0);
 // y = ReLU?(x*scale + shift (+ residual)) per channel (eval-mode BN, or any affine epilogue)
 hipError_t bn_apply(const void* x, const void* residual, void* y, int dtype, const float* scale, const float* shift,
                     int64_t M, int C, int relu, hipStream_t s);

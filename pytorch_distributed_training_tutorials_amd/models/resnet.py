@@ -81,7 +81,10 @@ class Bottleneck(nn.Module):
         if convbn._PRE:  # bn2's apply + ReLU run inside conv3's operand loads (PTDT_CONVBN_PRE, ops.convbn)
             return conv_bn_act(self.conv3, self.bn3, self.conv2(out), residual=identity, relu=True,
                                link=self.downsample is None, pre_bn=self.bn2)
-        out = bn_act(self.bn2, self.conv2(out), relu=True)
+        if convbn._C3X3 != "0":  # conv2 on the native 3x3 kernel, bn2's statistics in its epilogue
+            out = conv_bn_act(self.conv2, self.bn2, out, relu=True)
+        else:
+            out = bn_act(self.bn2, self.conv2(out), relu=True)
         # identity shortcut: the residual gradient goes straight into the producing BN's backward
         return conv_bn_act(self.conv3, self.bn3, out, residual=identity, relu=True, link=self.downsample is None)
 

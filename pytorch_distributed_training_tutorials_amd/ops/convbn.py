@@ -38,6 +38,13 @@ kernel recomputes the same operand from ``x`` (``pre=``), then ``pre_bn``'s own 
 activation is neither written, re-read nor saved (ResNet-50's conv2 -> bn2 -> ReLU -> conv3).
 ``PTDT_CONVBN_PRE_SKIP=KxN,...`` keeps single shapes on the composed path.
 
+3x3 convolutions (``PTDT_CONV3X3=0|on|auto``, default 0): a stride-1, padding-1 3x3 ``conv`` with channel counts
+that are multiples of 64 up to 1024 runs on ``conv3x3_bn.hip``, an implicit GEMM over the NHWC activation
+(K = 9 Cin, no im2col buffer) with the same statistics epilogue, and the BN runs only its apply pass. The
+backward is unchanged: the BN's native backward, then ``aten.convolution_backward`` on MIOpen. ``auto`` times
+the pair against MIOpen + ``bn_fwd_train`` once per (N, H, W, Cin, Cout) (tuning family ``conv3x3bn``).
+Not combined with ``PTDT_CONVBN_PRE`` (profiles/conv3x3_bn.md).
+
 Anything else -- stride 2, eval mode, fp32, NCHW, odd channel counts, CPU --
 takes the unfused ``bn_act(bn, conv(x))``. Where both apply, ``PTDT_CONVBN=auto`` (default)
 times the two once per shape on the live operands and keeps the faster (MIOpen's 1x1
@@ -72,6 +79,11 @@ _BWD_SKIP = {tuple(int(v) for v in t.split("x")) for t in os.environ.get("PTDT_C
 _PRE = os.environ.get("PTDT_CONVBN_PRE", "0") == "1"
 _PRE_SKIP = {tuple(int(v) for v in t.split("x")) for t in os.environ.get("PTDT_CONVBN_PRE_SKIP", "").split(",") if t}
 _CHOICE: dict[tuple, bool] = {}  # (M, K, N, tile) -> fused is faster (PTDT_CONVBN=auto)
+# stride-1 3x3 convolutions on the native implicit GEMM with the BN statistics in its epilogue
+# (csrc/kernels/conv3x3_bn.hip): 0 (default) never, on always, auto per-shape timing against MIOpen
+_C3X3 = os.environ.get("PTDT_CONV3X3", "0")
+if _C3X3 not in ("0", "on", "auto"):
+    raise ValueError(f"PTDT_CONV3X3={_C3X3!r}: expected 0, on or auto")
 
 
 def _tile(M: int, N: int, K: int) -> int:
@@ -271,49 +283,144 @@ def _time_us(fn, reps: int = 3) -> float:
     return best
 
 
-def _fused_wins(x: torch.Tensor, w: torch.Tensor, tile: int) -> bool:
-    """PTDT_CONVBN=auto: time, once per (M, K, N), the fused conv + statistics kernel + the BN apply
+def _timed_choice(family: str, key: tuple, mode: str, device, arms) -> bool:
+    """``mode`` on: fused. auto: time, once per ``key``, the fused conv + statistics kernel + the BN apply
     pass against MIOpen's convolution + the BN's statistics and apply passes on the live operands
-    (scratch statistics, no running-stat side effects), and keep the faster. Inside a graph capture an
-    unseen shape keeps the unfused path."""
-    n, cin, h, wd = x.shape
-    cout = w.shape[0]
-    key = (n * h * wd, cin, cout, tile)
-    if _MODE in ("1", "on"):
+    (``arms()`` builds the two callables: scratch statistics, no running-stat side effects), and keep the
+    faster. Inside a graph capture an unseen shape keeps the unfused path."""
+    if mode in ("1", "on"):
         return True
     from ..utils import tuning
 
-    hit = tuning.lookup("convbn", key)  # (a decision valid here: see tuning.lookup)
+    hit = tuning.lookup(family, key)  # (a decision valid here: see tuning.lookup)
     if hit is not None:
         return hit == "fused"
-    pin = tuning.pinned("convbn", key)
+    pin = tuning.pinned(family, key)
     if pin is not None:
         return pin == "fused"
     if torch.cuda.is_current_stream_capturing():
         return False
-    local = tuning.local_choice("convbn", key)
+    local = tuning.local_choice(family, key)
     if local is not None:  # timed before outside any scope: agree it, no second timing
-        return tuning.agree("convbn", key, local, ("unfused", "fused"), x.device) == "fused"
-    C = native()
-    x2 = x.detach().permute(0, 2, 3, 1).reshape(-1, cin)
-    w2 = w.detach().reshape(cout, cin)
-    tickets = torch.zeros(C.conv1x1_bn_num_tickets(key[0], cout, tile, cin), dtype=torch.int32, device=x.device)
-
-    def fused():
-        y2, st = C.conv1x1_bn_stats(x2, w2, None, None, None, None, None, 0.1, 1e-5, tickets, tile)
-        C.bn_fwd_apply(y2, st, None, True, False)
-
-    def plain():
-        y = torch.nn.functional.conv2d(x.detach(), w.detach())
-        C.bn_fwd_train(y, None, None, None, None, None, None, True, 0.1, 1e-5, None, False)
-
+        return tuning.agree(family, key, local, ("unfused", "fused"), device) == "fused"
+    fused, plain = arms()
     with torch.no_grad():  # interleaved, best of 5 each; near-ties (< 3 %) keep MIOpen's path
         tf, tp = float("inf"), float("inf")
         for _ in range(5):
             tf, tp = min(tf, _time_us(fused, 1)), min(tp, _time_us(plain, 1))
     local = "fused" if tf < 0.97 * tp else "unfused"
     # rank 0's choice on every rank: DDP replicas must run the same BN statistics path (utils/tuning.py)
-    return tuning.agree("convbn", key, local, ("unfused", "fused"), x.device) == "fused"
+    return tuning.agree(family, key, local, ("unfused", "fused"), device) == "fused"
+
+
+def _fused_wins(x: torch.Tensor, w: torch.Tensor, tile: int) -> bool:
+    """PTDT_CONVBN for a 1x1 convolution, per (M, K, N, tile): :func:`_timed_choice`."""
+    n, cin, h, wd = x.shape
+    cout = w.shape[0]
+    key = (n * h * wd, cin, cout, tile)
+
+    def arms():
+        C = native()
+        x2 = x.detach().permute(0, 2, 3, 1).reshape(-1, cin)
+        w2 = w.detach().reshape(cout, cin)
+        tickets = torch.zeros(C.conv1x1_bn_num_tickets(key[0], cout, tile, cin), dtype=torch.int32, device=x.device)
+
+        def fused():
+            y2, st = C.conv1x1_bn_stats(x2, w2, None, None, None, None, None, 0.1, 1e-5, tickets, tile)
+            C.bn_fwd_apply(y2, st, None, True, False)
+
+        def plain():
+            y = torch.nn.functional.conv2d(x.detach(), w.detach())
+            C.bn_fwd_train(y, None, None, None, None, None, None, True, 0.1, 1e-5, None, False)
+
+        return fused, plain
+
+    return _timed_choice("convbn", key, _MODE, x.device, arms)
+
+
+class _Conv3x3StatsFn(torch.autograd.Function):
+    """y = conv3x3(x, w), stride 1, padding 1 (NHWC bf16, csrc/kernels/conv3x3_bn.hip), and the [4, Cout] BN
+    statistics of y (non-differentiable). Backward: MIOpen's convolution_backward, as autograd would call it."""
+
+    @staticmethod
+    def forward(ctx, x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum: float, eps: float, tickets):
+        y, stats = native().conv3x3_bn_stats(x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum, eps,
+                                             tickets)
+        ctx.save_for_backward(x, w)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, gy, _gstats):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+        dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, mask)
+        return dx, dw, *([None] * 8)
+
+
+def _conv3x3_fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor) -> bool:
+    """PTDT_CONV3X3: a plain stride-1 3x3 convolution feeding a local training BatchNorm2d over the native
+    layout, a shape csrc/kernels/conv3x3_bn.hip takes."""
+    if _C3X3 == "0" or not (isinstance(bn, BatchNorm2d) and bn.training and bn.momentum is not None):
+        return False
+    if synchronizing(bn):
+        return False
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.padding_mode == "zeros"):
+        return False
+    if not (x.is_cuda and x.dim() == 4 and torch.is_autocast_enabled("cuda")
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    if x.shape[0] * x.shape[2] * x.shape[3] >= 2 ** 31:
+        return False
+    return native().conv3x3_bn_supported(conv.in_channels, conv.out_channels)
+
+
+def _conv3x3_wins(x: torch.Tensor, conv: nn.Conv2d) -> bool:
+    """PTDT_CONV3X3 for a 3x3 convolution, per (N, H, W, Cin, Cout): :func:`_timed_choice`. The weight is cast
+    only where a shape is timed: a cached choice costs no copy."""
+    n, cin, h, wd = x.shape
+    cout = conv.out_channels
+
+    def arms():
+        C = native()
+        xd = x.detach()
+        wdt = conv.weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        tickets = torch.zeros(C.conv3x3_bn_num_tickets(n * h * wd, cin, cout), dtype=torch.int32, device=x.device)
+
+        def fused():
+            y, st = C.conv3x3_bn_stats(xd, wdt, None, None, None, None, None, 0.1, 1e-5, tickets)
+            C.bn_fwd_apply(y, st, None, True, False)
+
+        def plain():
+            y = torch.nn.functional.conv2d(xd, wdt, padding=1)
+            C.bn_fwd_train(y, None, None, None, None, None, None, True, 0.1, 1e-5, None, False)
+
+        return fused, plain
+
+    return _timed_choice("conv3x3bn", (n, h, wd, cin, cout), _C3X3, x.device, arms)
+
+
+def _conv3x3_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, relu: bool, link: bool):
+    """The fused 3x3 path of conv_bn_act, or None: MIOpen won the timing (PTDT_CONV3X3=auto)."""
+    if not _conv3x3_wins(x, conv):
+        return None
+    w = cast_weight(conv.weight)
+    if not w.is_contiguous(memory_format=torch.channels_last):
+        w = w.contiguous(memory_format=torch.channels_last)  # [Cout, 3, 3, Cin] storage: a tiny copy
+    M = x.shape[0] * x.shape[2] * x.shape[3]
+    tickets = bn._gemm_tickets
+    need = native().conv3x3_bn_num_tickets(M, conv.in_channels, conv.out_channels)
+    if tickets.numel() < need or tickets.device != x.device:
+        raise RuntimeError(f"conv_bn_act: BN ticket buffer too small ({tickets.numel()} < {need}) or off-device")
+    track = bn.track_running_stats
+    y, stats = _Conv3x3StatsFn.apply(x, w, bn.weight, bn.bias, bn.running_mean if track else None,
+                                     bn.running_var if track else None, bn.num_batches_tracked if track else None,
+                                     float(bn.momentum), float(bn.eps), tickets)
+    return batch_norm_act(y, bn, None, relu, link, stats=stats)
 
 
 def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch.Tensor | None = None,
@@ -321,7 +428,8 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
     """``ReLU?(bn(conv(x)) + residual)``; a stride-1 1x1 ``conv`` feeding an ops.norm.BatchNorm2d in
     training under bf16 autocast computes the BN statistics in its GEMM epilogue. ``pre_bn``: ``x`` is the raw
     input of that BatchNorm and ``conv`` takes ``ReLU(pre_bn(x))``, applied inside the convolution's kernels
-    where PTDT_CONVBN_PRE allows (module docstring), else composed."""
+    where PTDT_CONVBN_PRE allows (module docstring), else composed. A stride-1 3x3 ``conv`` (no residual, no
+    ``pre_bn``) takes the native implicit GEMM where PTDT_CONV3X3 allows."""
     if pre_bn is not None:
         if not (_fusable(conv, bn, x, residual) and _pre_fusable(conv, pre_bn, x)):
             from ..models.resnet import bn_act
@@ -342,6 +450,10 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
             bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
             bn.num_batches_tracked if track else None, float(bn.momentum), float(bn.eps), tickets, clink)
         return batch_norm_act(y, bn, residual, relu, link, stats=stats, conv_link=clink)
+    if residual is None and _conv3x3_fusable(conv, bn, x):
+        out = _conv3x3_bn_act(conv, bn, x, relu, link)
+        if out is not None:
+            return out
     if not _fusable(conv, bn, x, residual):
         from ..models.resnet import bn_act
 

@@ -1,8 +1,9 @@
 """Rank-consistent, reproducible kernel-engine choices.
 
-Two selectors time competing kernels on first use of a shape: plain big bf16 GEMMs
-(ops/linear.py: gemm_big.hip vs hipBLASLt) and 1x1 conv + BN statistics
-(ops/convbn.py: fused native kernel vs MIOpen + BN pass). Timing is noisy, so on
+Three selectors time competing kernels on first use of a shape: plain big bf16 GEMMs
+(ops/linear.py: gemm_big.hip vs hipBLASLt), 1x1 conv + BN statistics
+(ops/convbn.py: fused native kernel vs MIOpen + BN pass) and, with PTDT_CONV3X3=auto, 3x3 conv
++ BN statistics (family ``conv3x3bn``, the same pair of arms). Timing is noisy, so on
 their own two DDP ranks could pick different kernels for one shape -- different
 bf16 rounding, different BN statistics merges, replicas that are no longer
 bit-identical. Here:
@@ -41,9 +42,10 @@ import zlib
 import torch
 
 _TABLE: dict | None = None
-_DECIDED: dict[str, dict[str, str]] = {"linear": {}, "convbn": {}}  # everything decided (choices())
-_AGREED: dict[str, dict[str, str]] = {"linear": {}, "convbn": {}}   # pinned or agreed in a scope: valid everywhere
-_LOCAL: dict[str, dict[str, str]] = {"linear": {}, "convbn": {}}    # this rank's own timing, outside any scope
+_FAMILIES = ("linear", "convbn", "conv3x3bn")
+_DECIDED: dict[str, dict[str, str]] = {f: {} for f in _FAMILIES}  # everything decided (choices())
+_AGREED: dict[str, dict[str, str]] = {f: {} for f in _FAMILIES}   # pinned or agreed in a scope: valid everywhere
+_LOCAL: dict[str, dict[str, str]] = {f: {} for f in _FAMILIES}    # this rank's own timing, outside any scope
 
 
 def _table() -> dict:
