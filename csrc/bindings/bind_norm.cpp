@@ -354,6 +354,46 @@ std::vector<Tensor> conv3x3_bn_stats_(Tensor x, Tensor w, c10::optional<Tensor> 
   return {y, stats};
 }
 
+bool conv3x3_bwd_supported_(int64_t Cin, int64_t Cout) {
+  return Cin >= 64 && Cout >= 64 && Cin <= 1024 && Cout <= 1024 && conv3x3_bwd_supported((int)Cin, (int)Cout);
+}
+
+// Backward of BN(conv3x3(x)) (stride 1, padding 1) from bn_bwd_reduce's (g, coef): g, y [N, Cout, H, W],
+// x [N, Cin, H, W], w [Cout, Cin, 3, 3], all channels_last bf16; returns (dx, dw) in the layouts of x and w.
+// tile: the weight-gradient instance (0: by shape).
+std::vector<Tensor> conv3x3_bwd_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor coef, int64_t tile) {
+  TORCH_CHECK(g.is_cuda() && y.is_cuda() && x.is_cuda() && w.is_cuda() && coef.is_cuda() &&
+                  y.device() == g.device() && x.device() == g.device() && w.device() == g.device() &&
+                  coef.device() == g.device(),
+              "conv3x3_bwd: GPU operands on one device");
+  TORCH_CHECK(g.dim() == 4 && y.sizes() == g.sizes() && x.dim() == 4 && w.dim() == 4 && w.size(2) == 3 &&
+                  w.size(3) == 3 && x.size(1) == w.size(1) && g.size(1) == w.size(0) && x.size(0) == g.size(0) &&
+                  x.size(2) == g.size(2) && x.size(3) == g.size(3),
+              "conv3x3_bwd: g, y [N, Cout, H, W], x [N, Cin, H, W], w [Cout, Cin, 3, 3]");
+  for (const Tensor* t : {&g, &y, &x, &w})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv3x3_bwd: channels_last-contiguous, 16-B aligned bf16 operands");
+  const int64_t B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = w.size(0);
+  const int64_t M = B * H * W;
+  TORCH_CHECK(conv3x3_bwd_supported_(Cin, Cout), "conv3x3_bwd: (Cin, Cout) = (", Cin, ", ", Cout,
+              ") must be multiples of 64 in 64 .. 1024");
+  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.dim() == 2 && coef.size(0) == 3 &&
+                  coef.size(1) == Cout && reinterpret_cast<uintptr_t>(coef.data_ptr()) % 16 == 0,
+              "conv3x3_bwd: coef [3, Cout] float, contiguous, 16-byte aligned");
+  TORCH_CHECK(M >= 1 && M < (1LL << 31), "conv3x3_bwd: 1 <= N H W < 2^31");
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128, "conv3x3_bwd: tile 0 (by shape), 64 or 128");
+  c10::hip::HIPGuard guard(g.device().index());
+  Tensor dx = at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor dw = at::empty_like(w, w.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor ws = at::empty({conv3x3_bwd_ws_floats((int)M, (int)Cin, (int)Cout, (int)tile)}, g.options().dtype(at::kFloat));
+  hip_check(conv3x3_bwd(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), coef.data_ptr<float>(), dx.data_ptr(),
+                        dw.data_ptr(), ws.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
+                        cur_stream(g), (int)tile),
+            "conv3x3_bwd");
+  return {dx, dw};
+}
+
 // The checks, kernel arguments and output tensors of a backward launch; the caller launches, with
 // `guard` still on x's device. reduce_only: g goes out through dres (want_dres is true), dx stays null.
 // with_coef: dwb is [5, C] = dweight, dbias, A, B, C with coef_a/b/c on its last three rows; else
@@ -701,6 +741,10 @@ void bind_norm(py::module_& m) {
   m.def("conv3x3_bn_supported", &conv3x3_bn_supported_, py::arg("Cin"), py::arg("Cout"));
   m.def("conv3x3_bn_num_tickets", &conv3x3_bn_num_tickets_, py::arg("M"), py::arg("Cin"), py::arg("Cout"),
         py::arg("tile") = 0);
+  m.def("conv3x3_bwd", &conv3x3_bwd_,
+        "fused BN-apply + 3x3 conv (stride 1, padding 1, NHWC bf16) data and weight gradients: (dx, dw)",
+        py::arg("g"), py::arg("y"), py::arg("x"), py::arg("w"), py::arg("coef"), py::arg("tile") = 0);
+  m.def("conv3x3_bwd_supported", &conv3x3_bwd_supported_, py::arg("Cin"), py::arg("Cout"));
   m.def("conv1x1_bwd_tiled_supported", &conv1x1_bwd_tiled_supported_);
   m.def("conv1x1_bwd_tiled_splits", [](int64_t M, int64_t K, int64_t N) {
     const bool ok = M >= 1 && M < (1LL << 31) && conv1x1_bwd_tiled_supported_(K, N);

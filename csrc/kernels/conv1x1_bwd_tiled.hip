@@ -27,17 +27,12 @@
 // that sticks out of K or N (K or N an odd multiple of 64) reads clamped, valid columns and stores
 // nothing for them.
 #include "common.h"
+#include "conv_bwd_tile.h"
 #include "kernels.h"
 #include "lds_tile.h"
 
 namespace ptdt {
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
 
 constexpr int kThreads = 256;
 constexpr int kTM = 128;            // rows of a dX block
@@ -48,56 +43,6 @@ constexpr int kLds = 4 * kImg;      // two buffers of two images: 64 KiB
 constexpr int kTargetWgs = 384;     // weight-gradient grid: 1.5 workgroups per CU of a 256-CU part
 constexpr int kMinBlocks = 4;       // row blocks per split at least (amortises the 64-KiB partial)
 constexpr int64_t kWsFloats = 8 << 20;  // workspace cap (32 MiB) unless one partial alone is larger
-
-struct Coef8 {
-  f32x4_t a[2], b[2], c[2];
-};
-// coefficients of channels n .. n + 7 (n % 8 == 0)
-__device__ __forceinline__ Coef8 load_coef(const float* __restrict__ coef, int N, int n) {
-  Coef8 k;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    k.a[h] = *reinterpret_cast<const f32x4_t*>(coef + n + 4 * h);
-    k.b[h] = *reinterpret_cast<const f32x4_t*>(coef + N + n + 4 * h);
-    k.c[h] = *reinterpret_cast<const f32x4_t*>(coef + 2 * (int64_t)N + n + 4 * h);
-  }
-  return k;
-}
-// 8 channels of dY from 16-B chunks of g and y
-__device__ __forceinline__ u32x4_t dy_chunk(u32x4_t gv, u32x4_t yv, const Coef8& k, bool valid) {
-  float d[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float gg = bf16_to_f32((uint16_t)(gv[e >> 1] >> (16 * (e & 1))));
-    const float yy = bf16_to_f32((uint16_t)(yv[e >> 1] >> (16 * (e & 1))));
-    d[e] = valid ? fmaf(k.a[e >> 2][e & 3], gg, fmaf(k.b[e >> 2][e & 3], yy, k.c[e >> 2][e & 3])) : 0.f;
-  }
-  u32x4_t pk;
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    const f32x2_t f = {d[2 * h], d[2 * h + 1]};
-    pk[h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
-  }
-  return pk;
-}
-
-// LDS-DMA of a [64][128] bf16 image: columns c0 .. c0 + 127 of the rows row_of(r) of a matrix with rows
-// ld elements apart; 16-B chunks past the matrix's last one (cmax) re-read that one.
-template <class RowOf>
-__device__ __forceinline__ void stage_image(const uint16_t* __restrict__ src, int64_t ld, int c0, int cmax,
-                                            uint8_t* img, int wid, int lane, RowOf row_of) {
-  stage_rows<64, 256, kThreads>(src, ld, c0, img, wid, lane, row_of, [=](int e) { return c0 + e < cmax ? e : cmax - c0; });
-}
-
-// MFMA fragment of the transpose of a [64][128] image: lane fr of a 16-lane group receives, for
-// reduction rows rb0 .. rb0 + 7 (rb0 = rb - tq), the column that lane group fr >> 2 addresses, element
-// fr & 3. (chunk, half): the 8 bytes this lane addresses in row rb and row rb + 4.
-__device__ __forceinline__ bf16x8_t read_tr(const uint8_t* img, int rb, int chunk, int half) {
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + tile_off<256>(rb, chunk) + 8 * half));
-  const s16x4_t hi =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + tile_off<256>(rb + 4, chunk) + 8 * half));
-  return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // The fragment of the recomputed operand a = bf16(max(fmaf(x, scale, shift), 0)) (conv1x1_pre.hip) from a
 // read_tr fragment of x: one channel (this lane's scale / shift) over 8 rows.
@@ -144,7 +89,7 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dx_kernel(
     ck = load_coef(coef, N, kTS * t + 8 * cc);
   };
   auto stage = [&](int t, uint8_t* img) {
-    stage_image(W, K, k0, K - 8, img, w, lane, [&](int r) { return kTS * t + r; });
+    stage_image<kThreads>(W, K, k0, K - 8, img, w, lane, [&](int r) { return kTS * t + r; });
   };
 
   f32x4_t acc[4][4];  // [channel tile j][row tile i]
@@ -245,7 +190,7 @@ __global__ void __launch_bounds__(kThreads, 2) conv1x1_bwd_tiled_dw_kernel(
     }
   };
   auto stage = [&](int b, uint8_t* img) {
-    stage_image(X, K, k0, K - 8, img, w, lane, [&](int r) {
+    stage_image<kThreads>(X, K, k0, K - 8, img, w, lane, [&](int r) {
       const int64_t m = (int64_t)b * kTS + r;
       return m < M ? m : (int64_t)M - 1;  // times dY = 0
     });

@@ -30,6 +30,10 @@
 //   channel tile (bn_merge.h, tickets re-armed to zero), bn_finish_channel.
 // Rows m >= M are computed from pixel M - 1, neither stored nor counted. A channel tile that sticks out of Cout
 // reads valid weight rows and stores nothing for them.
+//
+// Backward: the BN's native backward, then MIOpen's convolution_backward; or, with PTDT_CONV3X3_BWD=1,
+// conv3x3_bwd.hip, which takes this kernel's raw Y (the BN applies later) and the BN's reduce-pass coefficients
+// and forms dY = A g + B y + C on the same kind of register stage, with the same tap masks.
 #include "bn_finish.h"
 #include "bn_merge.h"
 #include "common.h"

@@ -717,6 +717,17 @@ int64_t conv3x3_bn_ws_floats(int M, int Cin, int Cout, int tile = 0);
 int64_t conv3x3_bn_num_tickets(int M, int Cin, int Cout, int tile = 0);
 hipError_t conv3x3_bn_stats(const void* x, const void* w, void* y, int N, int H, int W, int Cin, int Cout,
                             GemmBnEpi e, hipStream_t s, int tile = 0);
+// Backward of BN(conv3x3(x)), stride 1, padding 1 (csrc/kernels/conv3x3_bwd.hip), as conv1x1_bwd_tiled: dY =
+// A g + B y + C formed on the operand paths of an implicit-GEMM data gradient and a split-M weight gradient
+// (ws[splits][Cout][9 Cin] partials, splits a function of the shape and `tile` only), then conv1x1_bwd_merge.
+// g, y [N, H, W, Cout], x, dx [N, H, W, Cin], w, dw [Cout, 3, 3, Cin] bf16, all 16-B aligned; coef [3, Cout].
+// Shapes as conv3x3_bn_supported. tile: the weight-gradient instance, 0 (chosen from the shape), 64 or 128;
+// the same value goes to the sizing and the launch.
+bool conv3x3_bwd_supported(int Cin, int Cout);
+int conv3x3_bwd_splits(int M, int Cin, int Cout, int tile = 0);
+int64_t conv3x3_bwd_ws_floats(int M, int Cin, int Cout, int tile = 0);
+hipError_t conv3x3_bwd(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
+                       void* dw, float* ws, int N, int H, int W, int Cin, int Cout, hipStream_t s, int tile = 0);
 // y = ReLU?(x*scale + shift (+ residual)) per channel (eval-mode BN, or any affine epilogue)
 hipError_t bn_apply(const void* x, const void* residual, void* y, int dtype, const float* scale, const float* shift,
                     int64_t M, int C, int relu, hipStream_t s);

@@ -81,7 +81,8 @@ class Bottleneck(nn.Module):
         if convbn._PRE:  # bn2's apply + ReLU run inside conv3's operand loads (PTDT_CONVBN_PRE, ops.convbn)
             return conv_bn_act(self.conv3, self.bn3, self.conv2(out), residual=identity, relu=True,
                                link=self.downsample is None, pre_bn=self.bn2)
-        if convbn._C3X3 != "0":  # conv2 on the native 3x3 kernel, bn2's statistics in its epilogue
+        if convbn._C3X3 != "0" or convbn._C3X3_BWD:  # conv2 on the native 3x3 kernels: bn2's statistics in the
+            # forward's epilogue (PTDT_CONV3X3), bn2's backward applied inside conv2's (PTDT_CONV3X3_BWD)
             out = conv_bn_act(self.conv2, self.bn2, out, relu=True)
         else:
             out = bn_act(self.bn2, self.conv2(out), relu=True)

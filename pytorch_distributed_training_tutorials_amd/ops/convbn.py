@@ -41,9 +41,15 @@ activation is neither written, re-read nor saved (ResNet-50's conv2 -> bn2 -> Re
 3x3 convolutions (``PTDT_CONV3X3=0|on|auto``, default 0): a stride-1, padding-1 3x3 ``conv`` with channel counts
 that are multiples of 64 up to 1024 runs on ``conv3x3_bn.hip``, an implicit GEMM over the NHWC activation
 (K = 9 Cin, no im2col buffer) with the same statistics epilogue, and the BN runs only its apply pass. The
-backward is unchanged: the BN's native backward, then ``aten.convolution_backward`` on MIOpen. ``auto`` times
+backward is the BN's native backward, then ``aten.convolution_backward`` on MIOpen. ``auto`` times
 the pair against MIOpen + ``bn_fwd_train`` once per (N, H, W, Cin, Cout) (tuning family ``conv3x3bn``).
 Not combined with ``PTDT_CONVBN_PRE`` (profiles/conv3x3_bn.md).
+
+3x3 backward (``PTDT_CONV3X3_BWD=0|1``, default 0): the same convolutions get a :class:`ConvBwdLink`, behind the
+native forward or, where ``PTDT_CONV3X3`` is 0 or ``auto`` chose MIOpen, behind MIOpen's forward with the BN's own
+statistics: the BN runs only its reduce pass and ``conv3x3_bwd.hip`` forms ``dY = A g + B y + C`` on the operand
+paths of its data- and weight-gradient kernels, so ``dY`` is neither written nor read back.
+``PTDT_CONV3X3_BWD_SKIP=CinxCout,...`` keeps single shapes on MIOpen's backward (profiles/conv3x3_bwd.md).
 
 Anything else -- stride 2, eval mode, fp32, NCHW, odd channel counts, CPU --
 takes the unfused ``bn_act(bn, conv(x))``. Where both apply, ``PTDT_CONVBN=auto`` (default)
@@ -84,6 +90,13 @@ _CHOICE: dict[tuple, bool] = {}  # (M, K, N, tile) -> fused is faster (PTDT_CONV
 _C3X3 = os.environ.get("PTDT_CONV3X3", "0")
 if _C3X3 not in ("0", "on", "auto"):
     raise ValueError(f"PTDT_CONV3X3={_C3X3!r}: expected 0, on or auto")
+# the same convolutions' backward linked to the BN's (csrc/kernels/conv3x3_bwd.hip), behind either forward
+_C3X3_BWD = os.environ.get("PTDT_CONV3X3_BWD", "0")
+if _C3X3_BWD not in ("0", "1"):
+    raise ValueError(f"PTDT_CONV3X3_BWD={_C3X3_BWD!r}: expected 0 or 1")
+_C3X3_BWD = _C3X3_BWD == "1"
+_C3X3_BWD_SKIP = {tuple(int(v) for v in t.split("x"))
+                  for t in os.environ.get("PTDT_CONV3X3_BWD_SKIP", "").split(",") if t}
 
 
 def _tile(M: int, N: int, K: int) -> int:
@@ -338,31 +351,69 @@ def _fused_wins(x: torch.Tensor, w: torch.Tensor, tile: int) -> bool:
     return _timed_choice("convbn", key, _MODE, x.device, arms)
 
 
+def _conv3x3_link(cin: int, cout: int) -> ConvBwdLink | None:
+    """The link for a cin -> cout 3x3 convolution (PTDT_CONV3X3_BWD), or None."""
+    if not (_C3X3_BWD and torch.is_grad_enabled()) or (cin, cout) in _C3X3_BWD_SKIP:
+        return None
+    return ConvBwdLink() if native().conv3x3_bwd_supported(cin, cout) else None
+
+
+def _conv3x3_backward(ctx, gy, x, w, y):
+    """(dx, dw) of y = conv3x3(x, w): linked (gy is the BN's masked gradient g, ctx.link holds the coefficients:
+    csrc/kernels/conv3x3_bwd.hip) or plain (gy is dY: MIOpen, as autograd would call it)."""
+    link = ctx.link
+    gy = gy.contiguous(memory_format=torch.channels_last)
+    if link is not None and link.coef is not None:
+        coef, link.coef = link.coef, None
+        dx, dw = native().conv3x3_bwd(gy, y, x, w, coef)
+        return (dx if ctx.needs_input_grad[0] else None), (dw if ctx.needs_input_grad[1] else None)
+    mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+    dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, mask)
+    return dx, dw
+
+
 class _Conv3x3StatsFn(torch.autograd.Function):
     """y = conv3x3(x, w), stride 1, padding 1 (NHWC bf16, csrc/kernels/conv3x3_bn.hip), and the [4, Cout] BN
-    statistics of y (non-differentiable). Backward: MIOpen's convolution_backward, as autograd would call it."""
+    statistics of y (non-differentiable). Backward: :func:`_conv3x3_backward`."""
 
     @staticmethod
-    def forward(ctx, x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum: float, eps: float, tickets):
+    def forward(ctx, x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum: float, eps: float, tickets,
+                link=None):
         y, stats = native().conv3x3_bn_stats(x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum, eps,
                                              tickets)
-        ctx.save_for_backward(x, w)
+        ctx.link = link
+        ctx.save_for_backward(x, w, y if link is not None else None)
         ctx.mark_non_differentiable(stats)
         return y, stats
 
     @staticmethod
     def backward(ctx, gy, _gstats):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
-        dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, mask)
-        return dx, dw, *([None] * 8)
+        x, w, y = ctx.saved_tensors
+        return *_conv3x3_backward(ctx, gy, x, w, y), *([None] * 9)
+
+
+class _Conv3x3LinkedFn(torch.autograd.Function):
+    """y = conv3x3(x, w) on MIOpen (NHWC bf16) with the linked backward (PTDT_CONV3X3_BWD where PTDT_CONV3X3 is 0 or
+    MIOpen's forward won the timing): the backward does not depend on who computed y."""
+
+    @staticmethod
+    def forward(ctx, x, w, link):
+        y = torch.nn.functional.conv2d(x, w, padding=1).contiguous(memory_format=torch.channels_last)
+        ctx.link = link
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, y = ctx.saved_tensors
+        return *_conv3x3_backward(ctx, gy, x, w, y), None
 
 
 def _conv3x3_fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor) -> bool:
-    """PTDT_CONV3X3: a plain stride-1 3x3 convolution feeding a local training BatchNorm2d over the native
-    layout, a shape csrc/kernels/conv3x3_bn.hip takes."""
-    if _C3X3 == "0" or not (isinstance(bn, BatchNorm2d) and bn.training and bn.momentum is not None):
+    """PTDT_CONV3X3 / PTDT_CONV3X3_BWD: a plain stride-1 3x3 convolution feeding a local training BatchNorm2d over
+    the native layout, a shape csrc/kernels/conv3x3_bn.hip and conv3x3_bwd.hip take."""
+    if (_C3X3 == "0" and not _C3X3_BWD) or not (isinstance(bn, BatchNorm2d) and bn.training
+                                                 and bn.momentum is not None):
         return False
     if synchronizing(bn):
         return False
@@ -405,12 +456,17 @@ def _conv3x3_wins(x: torch.Tensor, conv: nn.Conv2d) -> bool:
 
 
 def _conv3x3_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, relu: bool, link: bool):
-    """The fused 3x3 path of conv_bn_act, or None: MIOpen won the timing (PTDT_CONV3X3=auto)."""
-    if not _conv3x3_wins(x, conv):
+    """The native 3x3 paths of conv_bn_act: the fused forward (PTDT_CONV3X3) and / or the linked backward
+    (PTDT_CONV3X3_BWD); None: neither applies (the knob is 0 or MIOpen won the timing; no link)."""
+    clink = _conv3x3_link(conv.in_channels, conv.out_channels)
+    fused = _C3X3 != "0" and _conv3x3_wins(x, conv)
+    if not fused and clink is None:
         return None
     w = cast_weight(conv.weight)
     if not w.is_contiguous(memory_format=torch.channels_last):
         w = w.contiguous(memory_format=torch.channels_last)  # [Cout, 3, 3, Cin] storage: a tiny copy
+    if not fused:  # MIOpen's forward, the BN's own statistics, the linked backward
+        return batch_norm_act(_Conv3x3LinkedFn.apply(x, w, clink), bn, None, relu, link, conv_link=clink)
     M = x.shape[0] * x.shape[2] * x.shape[3]
     tickets = bn._gemm_tickets
     need = native().conv3x3_bn_num_tickets(M, conv.in_channels, conv.out_channels)
@@ -419,8 +475,8 @@ def _conv3x3_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, relu: bool,
     track = bn.track_running_stats
     y, stats = _Conv3x3StatsFn.apply(x, w, bn.weight, bn.bias, bn.running_mean if track else None,
                                      bn.running_var if track else None, bn.num_batches_tracked if track else None,
-                                     float(bn.momentum), float(bn.eps), tickets)
-    return batch_norm_act(y, bn, None, relu, link, stats=stats)
+                                     float(bn.momentum), float(bn.eps), tickets, clink)
+    return batch_norm_act(y, bn, None, relu, link, stats=stats, conv_link=clink)
 
 
 def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch.Tensor | None = None,
@@ -429,7 +485,8 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
     training under bf16 autocast computes the BN statistics in its GEMM epilogue. ``pre_bn``: ``x`` is the raw
     input of that BatchNorm and ``conv`` takes ``ReLU(pre_bn(x))``, applied inside the convolution's kernels
     where PTDT_CONVBN_PRE allows (module docstring), else composed. A stride-1 3x3 ``conv`` (no residual, no
-    ``pre_bn``) takes the native implicit GEMM where PTDT_CONV3X3 allows."""
+    ``pre_bn``) takes the native implicit GEMM where PTDT_CONV3X3 allows, and the native linked backward where
+    PTDT_CONV3X3_BWD does."""
     if pre_bn is not None:
         if not (_fusable(conv, bn, x, residual) and _pre_fusable(conv, pre_bn, x)):
             from ..models.resnet import bn_act
