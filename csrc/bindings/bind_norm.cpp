@@ -305,6 +305,92 @@ std::vector<Tensor> conv1x1_pre_bn_stats_(Tensor x, Tensor pre_stats, Tensor w, 
   return {y, stats};
 }
 
+bool conv1x1_s2_supported_(int64_t K, int64_t N) {
+  return K >= 64 && N >= 64 && K <= 4096 && N <= 4096 && conv1x1_s2_supported((int)K, (int)N);
+}
+
+int64_t conv1x1_s2_num_tickets_(int64_t Mout, int64_t K, int64_t N) {
+  const bool ok = Mout >= 1 && Mout < (1LL << 31) && conv1x1_s2_supported_(K, N);
+  return ok ? conv1x1_s2_num_tickets((int)Mout, (int)K, (int)N) : 0;
+}
+
+// Stride-2 1x1 convolution (padding 0, no bias) of a channels_last bf16 activation + the training BatchNorm's
+// batch statistics of the output, as conv1x1_bn_stats: x [Nb, Cin, H, W] channels_last, w [Cout, Cin]; returns
+// (y [Nb, Cout, Ho, Wo] bf16 channels_last, stats [4, Cout]), Ho = (H + 1) / 2, Wo = (W + 1) / 2.
+std::vector<Tensor> conv1x1_s2_bn_stats_(Tensor x, Tensor w, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
+                                         c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
+                                         c10::optional<Tensor> num_batches_tracked, double momentum, double eps,
+                                         Tensor tickets) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.device() == w.device(),
+              "conv1x1_s2_bn_stats: GPU operands on one device");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 2 && x.size(1) == w.size(1),
+              "conv1x1_s2_bn_stats: x [Nb, Cin, H, W], w [Cout, Cin]");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  w.scalar_type() == at::kBFloat16 && w.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "conv1x1_s2_bn_stats: channels_last-contiguous x, contiguous w, 16-B aligned bf16");
+  const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w.size(0);
+  const int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2, M = B * Ho * Wo;
+  TORCH_CHECK(conv1x1_s2_supported_(K, N), "conv1x1_s2_bn_stats: (Cin, Cout) = (", K, ", ", N,
+              ") must be multiples of 64 in 64 .. 4096");
+  TORCH_CHECK(M >= 1 && B * H * W < (1LL << 31), "conv1x1_s2_bn_stats: 1 <= Nb H W < 2^31");
+  const int64_t need = conv1x1_s2_num_tickets((int)M, (int)K, (int)N);
+  TORCH_CHECK(tickets.is_cuda() && tickets.device() == x.device() && tickets.scalar_type() == at::kInt &&
+                  tickets.is_contiguous() && tickets.numel() >= need,
+              "conv1x1_s2_bn_stats: tickets must be a zeroed int32 tensor of >= ", need, " elements");
+  c10::hip::HIPGuard guard(x.device().index());
+  Tensor y = at::empty({B, N, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor stats = at::empty({4, N}, x.options().dtype(at::kFloat));
+  Tensor ws = at::empty({conv1x1_s2_ws_floats((int)M, (int)K, (int)N)}, x.options().dtype(at::kFloat));
+  GemmBnEpi e{};
+  e.ws = ws.data_ptr<float>();
+  e.tickets = tickets.data_ptr<int>();
+  fill_bn_params(e.p, (int)N, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps);
+  split_stats(e.p, stats.data_ptr<float>(), N);
+  hip_check(conv1x1_s2_bn_stats(x.data_ptr(), w.data_ptr(), y.data_ptr(), (int)B, (int)H, (int)W, (int)K, (int)N, e,
+                                cur_stream(x)),
+            "conv1x1_s2_bn_stats");
+  return {y, stats};
+}
+
+// Backward of BN(conv1x1(x, stride 2)) from bn_bwd_reduce's (g, coef): g, y [Nb, Cout, Ho, Wo] and x
+// [Nb, Cin, H, W] channels_last bf16, w [Cout, Cin]; returns (dx like x, every pixel written, dw [Cout, Cin]).
+std::vector<Tensor> conv1x1_s2_bwd_(Tensor g, Tensor y, Tensor x, Tensor w, Tensor coef) {
+  TORCH_CHECK(g.is_cuda() && y.is_cuda() && x.is_cuda() && w.is_cuda() && coef.is_cuda() &&
+                  y.device() == g.device() && x.device() == g.device() && w.device() == g.device() &&
+                  coef.device() == g.device(),
+              "conv1x1_s2_bwd: GPU operands on one device");
+  TORCH_CHECK(g.dim() == 4 && y.sizes() == g.sizes() && x.dim() == 4 && w.dim() == 2 && x.size(1) == w.size(1) &&
+                  g.size(1) == w.size(0) && x.size(0) == g.size(0) && g.size(2) == (x.size(2) + 1) / 2 &&
+                  g.size(3) == (x.size(3) + 1) / 2,
+              "conv1x1_s2_bwd: g, y [Nb, Cout, (H + 1) / 2, (W + 1) / 2], x [Nb, Cin, H, W], w [Cout, Cin]");
+  for (const Tensor* t : {&g, &y, &x})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv1x1_s2_bwd: channels_last-contiguous, 16-B aligned bf16 activations");
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "conv1x1_s2_bwd: contiguous, 16-B aligned bf16 w");
+  const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w.size(0);
+  const int64_t M = B * g.size(2) * g.size(3);
+  TORCH_CHECK(conv1x1_s2_supported_(K, N), "conv1x1_s2_bwd: (Cin, Cout) = (", K, ", ", N,
+              ") must be multiples of 64 in 64 .. 4096");
+  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.dim() == 2 && coef.size(0) == 3 &&
+                  coef.size(1) == N && reinterpret_cast<uintptr_t>(coef.data_ptr()) % 16 == 0,
+              "conv1x1_s2_bwd: coef [3, Cout] float, contiguous, 16-byte aligned");
+  TORCH_CHECK(M >= 1 && B * H * W < (1LL << 31), "conv1x1_s2_bwd: 1 <= Nb H W < 2^31");
+  c10::hip::HIPGuard guard(g.device().index());
+  Tensor dx = at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast));  // no memset
+  Tensor dw = at::empty({N, K}, w.options());
+  Tensor ws = at::empty({conv1x1_s2_bwd_ws_floats((int)M, (int)K, (int)N)}, g.options().dtype(at::kFloat));
+  hip_check(conv1x1_s2_bwd(g.data_ptr(), y.data_ptr(), x.data_ptr(), w.data_ptr(), coef.data_ptr<float>(),
+                           dx.data_ptr(), dw.data_ptr(), ws.data_ptr<float>(), (int)B, (int)H, (int)W, (int)K, (int)N,
+                           cur_stream(g)),
+            "conv1x1_s2_bwd");
+  return {dx, dw};
+}
+
 bool conv3x3_bn_supported_(int64_t Cin, int64_t Cout) {
   return Cin >= 64 && Cout >= 64 && Cin <= 1024 && Cout <= 1024 && conv3x3_bn_supported((int)Cin, (int)Cout);
 }
@@ -733,6 +819,16 @@ void bind_norm(py::module_& m) {
         py::arg("tickets"));
   m.def("conv1x1_pre_supported", &conv1x1_pre_supported_, py::arg("K"), py::arg("N"));
   m.def("conv1x1_pre_num_tickets", &conv1x1_pre_num_tickets_, py::arg("M"), py::arg("K"), py::arg("N"));
+  m.def("conv1x1_s2_bn_stats", &conv1x1_s2_bn_stats_,
+        "stride-2 1x1 conv (padding 0, NHWC bf16, gathered rows) + BN statistics of the output: (y, stats[4, Cout])",
+        py::arg("x"), py::arg("w"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("num_batches_tracked"), py::arg("momentum"), py::arg("eps"),
+        py::arg("tickets"));
+  m.def("conv1x1_s2_bwd", &conv1x1_s2_bwd_,
+        "fused BN-apply + stride-2 1x1 conv data and weight gradients, dx written completely: (dx, dw)",
+        py::arg("g"), py::arg("y"), py::arg("x"), py::arg("w"), py::arg("coef"));
+  m.def("conv1x1_s2_supported", &conv1x1_s2_supported_, py::arg("K"), py::arg("N"));
+  m.def("conv1x1_s2_num_tickets", &conv1x1_s2_num_tickets_, py::arg("Mout"), py::arg("K"), py::arg("N"));
   m.def("conv3x3_bn_stats", &conv3x3_bn_stats_,
         "3x3 conv (stride 1, padding 1, NHWC bf16 implicit GEMM) + BN statistics of the output: (y, stats[4, Cout])",
         py::arg("x"), py::arg("w"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),

@@ -707,6 +707,22 @@ int64_t conv1x1_pre_ws_floats(int M, int K, int N);
 int64_t conv1x1_pre_num_tickets(int M, int K, int N);
 hipError_t conv1x1_pre_bn_stats(const void* x, const float* scale, const float* shift, const void* w, void* y, int M,
                                 int K, int N, GemmBnEpi e, hipStream_t s);
+// Stride-2 1x1 convolution (padding 0) over NHWC bf16 plus the batch statistics of its own bf16 output as
+// gemm_bn_stats, and its backward as conv1x1_bwd_tiled (csrc/kernels/conv1x1_s2.hip): x, dx [Nb, H, W, K],
+// w, dw [N, K], y, g [Nb, Ho, Wo, N] with Ho = (H + 1) / 2, Wo = (W + 1) / 2, all 16-B aligned; coef [3, N].
+// K, N as conv1x1_bwd_tiled_supported; H, W >= 1; Nb H W < 2^31. Mout = Nb Ho Wo sizes the buffers: e.ws
+// conv1x1_s2_ws_floats floats, e.tickets conv1x1_s2_num_tickets zeroed ints (re-armed), the backward's ws
+// conv1x1_s2_bwd_ws_floats floats (splits a function of (Mout, K, N) only). dx is written completely: the
+// pixels no output row reads get +0.
+bool conv1x1_s2_supported(int K, int N);
+int64_t conv1x1_s2_ws_floats(int Mout, int K, int N);
+int64_t conv1x1_s2_num_tickets(int Mout, int K, int N);
+int conv1x1_s2_bwd_splits(int Mout, int K, int N);
+int64_t conv1x1_s2_bwd_ws_floats(int Mout, int K, int N);
+hipError_t conv1x1_s2_bn_stats(const void* x, const void* w, void* y, int Nb, int H, int W, int K, int N, GemmBnEpi e,
+                               hipStream_t s);
+hipError_t conv1x1_s2_bwd(const void* g, const void* y, const void* x, const void* w, const float* coef, void* dx,
+                          void* dw, float* ws, int Nb, int H, int W, int K, int N, hipStream_t s);
 // 3x3 convolution, stride 1, padding 1, as an implicit GEMM over NHWC bf16, plus the batch statistics of its own
 // bf16 output as gemm_bn_stats (csrc/kernels/conv3x3_bn.hip): x [N, H, W, Cin], w [Cout, 3, 3, Cin],
 // y [N, H, W, Cout], all 16-B aligned. Cin, Cout multiples of 64 in 64 .. 1024; 1 <= M = N H W < 2^31.

@@ -51,7 +51,16 @@ statistics: the BN runs only its reduce pass and ``conv3x3_bwd.hip`` forms ``dY 
 paths of its data- and weight-gradient kernels, so ``dY`` is neither written nor read back.
 ``PTDT_CONV3X3_BWD_SKIP=CinxCout,...`` keeps single shapes on MIOpen's backward (profiles/conv3x3_bwd.md).
 
-Anything else -- stride 2, eval mode, fp32, NCHW, odd channel counts, CPU --
+Stride-2 1x1 convolutions (``PTDT_CONVBN_S2=0|1``, default 0): a stride-(2, 2), padding-0 1x1 ``conv`` with
+channel counts that are multiples of 64 up to 4096 (the downsample branches of ResNet-50's layer2-4) runs on
+``conv1x1_s2.hip``: the stride-1 GEMM with the activation's rows gathered, the statistics in its epilogue, and
+the BN runs only its apply pass. Its backward follows ``PTDT_CONVBN_BWD`` / ``PTDT_CONVBN_BWD_SKIP``: linked (not
+``0``), the BN runs only its reduce pass, the data-gradient kernel writes every pixel of the dense ``dX`` once --
+a gathered row's gradient or zeros, no memset -- and the weight gradient gathers the same rows; else the BN's
+native backward and ``aten.convolution_backward``. No timing arm: ``1`` always takes the kernels
+(profiles/conv1x1_s2.md).
+
+Anything else -- other strides, eval mode, fp32, NCHW, odd channel counts, CPU --
 takes the unfused ``bn_act(bn, conv(x))``. Where both apply, ``PTDT_CONVBN=auto`` (default)
 times the two once per shape on the live operands and keeps the faster (MIOpen's 1x1
 forward kernels run close to HBM speed on some shapes, profiles/r3_convbn.md); ``on``
@@ -97,6 +106,11 @@ if _C3X3_BWD not in ("0", "1"):
 _C3X3_BWD = _C3X3_BWD == "1"
 _C3X3_BWD_SKIP = {tuple(int(v) for v in t.split("x"))
                   for t in os.environ.get("PTDT_CONV3X3_BWD_SKIP", "").split(",") if t}
+# stride-2 1x1 convolutions on the native gathered-row kernels, forward and backward (csrc/kernels/conv1x1_s2.hip)
+_S2 = os.environ.get("PTDT_CONVBN_S2", "0")
+if _S2 not in ("0", "1"):
+    raise ValueError(f"PTDT_CONVBN_S2={_S2!r}: expected 0 or 1")
+_S2 = _S2 == "1"
 
 
 def _tile(M: int, N: int, K: int) -> int:
@@ -247,6 +261,37 @@ class _PreConv1x1StatsFn(torch.autograd.Function):
                 *([None] * 6), dw2.view(cout, cin, 1, 1) if ctx.needs_input_grad[9] else None, *([None] * 9))
 
 
+class _Conv1x1S2StatsFn(torch.autograd.Function):
+    """y = conv1x1(x, w, stride 2) (NHWC bf16, csrc/kernels/conv1x1_s2.hip) and the [4, Cout] BN statistics of y
+    (non-differentiable). Backward: linked (gy is the BN's masked gradient g, ctx.link holds the coefficients) on
+    the same file's kernels, whose dx is dense; or plain (gy is dY: MIOpen, as autograd would call it)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bn_weight, bn_bias, running_mean, running_var, nbt, momentum: float, eps: float, tickets,
+                link=None):
+        y, stats = native().conv1x1_s2_bn_stats(x, w.reshape(w.shape[0], w.shape[1]), bn_weight, bn_bias,
+                                                running_mean, running_var, nbt, momentum, eps, tickets)
+        ctx.link = link
+        ctx.save_for_backward(x, w, y if link is not None else None)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, gy, _gstats):
+        x, w, y = ctx.saved_tensors
+        link = ctx.link
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        if link is not None and link.coef is not None:
+            coef, link.coef = link.coef, None
+            dx, dw = native().conv1x1_s2_bwd(gy, y, x, w.reshape(w.shape[0], w.shape[1]), coef)
+            dw = dw.view_as(w)
+        else:
+            mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+            dx, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [2, 2], [0, 0], [1, 1], False, [0, 0], 1,
+                                                            mask)
+        return (dx if ctx.needs_input_grad[0] else None), (dw if ctx.needs_input_grad[1] else None), *([None] * 9)
+
+
 def _pre_fusable(conv: nn.Conv2d, pre_bn: nn.Module, x: torch.Tensor) -> bool:
     """conv_bn_act(pre_bn=) on top of _fusable(conv, bn, x, residual): a local training BatchNorm2d over the
     native layout, grad mode (the fusion's point is the backward's saved activation), a shape with a kernel."""
@@ -259,12 +304,12 @@ def _pre_fusable(conv: nn.Conv2d, pre_bn: nn.Module, x: torch.Tensor) -> bool:
     return native().conv1x1_pre_supported(cin, cout)
 
 
-def _fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual) -> bool:
+def _fusable(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual, stride=(1, 1)) -> bool:
     if not (_ENABLED and isinstance(bn, BatchNorm2d) and bn.training and bn.momentum is not None):
         return False
     if synchronizing(bn):  # the epilogue's statistics (and the ConvBwdLink backward) are this rank's only
         return False
-    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == stride
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and conv.padding_mode == "zeros"):
         return False
@@ -479,6 +524,24 @@ def _conv3x3_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, relu: bool,
     return batch_norm_act(y, bn, None, relu, link, stats=stats, conv_link=clink)
 
 
+def _conv1x1_s2_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, relu: bool, link: bool):
+    """The native stride-2 1x1 path of conv_bn_act (PTDT_CONVBN_S2): the gathered-row forward with the statistics
+    in its epilogue, the BN's apply pass, and the linked backward where PTDT_CONVBN_BWD allows."""
+    cin, cout = conv.in_channels, conv.out_channels
+    Mout = x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2)
+    tickets = bn._gemm_tickets
+    need = native().conv1x1_s2_num_tickets(Mout, cin, cout)
+    if tickets.numel() < need or tickets.device != x.device:
+        raise RuntimeError(f"conv_bn_act: BN ticket buffer too small ({tickets.numel()} < {need}) or off-device")
+    clink = ConvBwdLink() if _BWD and torch.is_grad_enabled() and (cin, cout) not in _BWD_SKIP else None
+    track = bn.track_running_stats
+    y, stats = _Conv1x1S2StatsFn.apply(x, cast_weight(conv.weight), bn.weight, bn.bias,
+                                       bn.running_mean if track else None, bn.running_var if track else None,
+                                       bn.num_batches_tracked if track else None, float(bn.momentum), float(bn.eps),
+                                       tickets, clink)
+    return batch_norm_act(y, bn, None, relu, link, stats=stats, conv_link=clink)
+
+
 def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch.Tensor | None = None,
                 relu: bool = False, link: bool = False, pre_bn: nn.Module | None = None) -> torch.Tensor:
     """``ReLU?(bn(conv(x)) + residual)``; a stride-1 1x1 ``conv`` feeding an ops.norm.BatchNorm2d in
@@ -486,7 +549,8 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
     input of that BatchNorm and ``conv`` takes ``ReLU(pre_bn(x))``, applied inside the convolution's kernels
     where PTDT_CONVBN_PRE allows (module docstring), else composed. A stride-1 3x3 ``conv`` (no residual, no
     ``pre_bn``) takes the native implicit GEMM where PTDT_CONV3X3 allows, and the native linked backward where
-    PTDT_CONV3X3_BWD does."""
+    PTDT_CONV3X3_BWD does. A stride-2, padding-0 1x1 ``conv`` (no residual, no ``pre_bn``) takes the native
+    gathered-row kernels where PTDT_CONVBN_S2 allows."""
     if pre_bn is not None:
         if not (_fusable(conv, bn, x, residual) and _pre_fusable(conv, pre_bn, x)):
             from ..models.resnet import bn_act
@@ -511,6 +575,9 @@ def conv_bn_act(conv: nn.Conv2d, bn: nn.Module, x: torch.Tensor, residual: torch
         out = _conv3x3_bn_act(conv, bn, x, relu, link)
         if out is not None:
             return out
+    if (_S2 and residual is None and _fusable(conv, bn, x, None, stride=(2, 2))
+            and native().conv1x1_s2_supported(conv.in_channels, conv.out_channels)):
+        return _conv1x1_s2_bn_act(conv, bn, x, relu, link)
     if not _fusable(conv, bn, x, residual):
         from ..models.resnet import bn_act
 
