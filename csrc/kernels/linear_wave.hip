@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
+#include "wave_kernel_rules.h"
 #include "wave_row_image.h"
 
 namespace ptdt {
@@ -20,10 +21,17 @@ size_t lds_bytes(const FusedMlpArgs& a, const PersistArgs& p) {  // two epoch in
   return (size_t)2 * wave_list_stride(p.num_samples, a.B) * sizeof(int) + 8 * sizeof(unsigned long long);
 }
 constexpr size_t kStaticLds = 512;  // layout F's static pair-exchange scratch (linear_wave_impl.h)
-// loss ring of layout F: (2 epochs + prefetch depth) steps x 64 lane shares
-size_t ring_bytes(const FusedMlpArgs& a, const PersistArgs& p) {
+// loss ring of layout F: (2 epochs + the kernel's batches in flight) steps x 64 lane shares
+size_t ring_bytes(const FusedMlpArgs& a, const PersistArgs& p, int depth = kWavePrefetch) {
   const int S = (p.num_samples + a.B - 1) / a.B;
-  return (size_t)(2 * S + kWavePrefetch) * 64 * sizeof(float);
+  return (size_t)(2 * S + depth) * 64 * sizeof(float);
+}
+// ring_fits decides with the generic kernel's depth; no kernel has a smaller ring than that one
+static_assert(lw::kWaveGatherDepth >= kWavePrefetch && lw::wave_gather_depth(2, 5, 1, kWaveGeneric, false) == kWavePrefetch,
+              "the generic kernels keep kWavePrefetch, the deepened ones have at least that");
+// batches in flight of the layout-F kernel a plan runs: the kernel's own constant (wave_kernel_rules.h)
+int gather_depth(const FusedMlpArgs& a, const PersistChoice& c, int var) {
+  return c.L == 0 ? lw::wave_gather_depth(c.R, c.kp, a.Dout, var, a.ar.world > 1) : kWavePrefetch;
 }
 
 // var: WaveKernelVariant (lean variants exist for layout F only; nullptr otherwise)
@@ -124,7 +132,10 @@ int linear_wave_variant(const FusedMlpArgs& a, const PersistArgs& p, const Persi
   if (env != nullptr && env[0] != '\0' && env[0] != '0') return kWaveGeneric;
   if (c.engine != kEngWave || !ring_fits(a, p, c) || stamps) return kWaveGeneric;
   if (a.B != 16 * c.R || p.num_samples % a.B != 0 || a.weight_decay != 0.f) return kWaveGeneric;
-  return has_mom && a.momentum != 0.f ? kWaveLeanMom : kWaveLeanPlain;
+  const int var = has_mom && a.momentum != 0.f ? kWaveLeanMom : kWaveLeanPlain;
+  // a deeper kernel's ring has a slot more per batch in flight: it must fit as well
+  if (lds_bytes(a, p) + ring_bytes(a, p, gather_depth(a, c, var)) + kStaticLds > 160 * 1024) return kWaveGeneric;
+  return var;
 }
 
 hipError_t linear_wave_prepare(PersistLaunch* L) {
@@ -132,10 +143,8 @@ hipError_t linear_wave_prepare(PersistLaunch* L) {
   const PersistChoice& c = L->choice;
   size_t lds = lds_bytes(a, L->p);
   L->p.loss_ring = 0;
-  if (ring_fits(a, L->p, c)) {
-    L->p.loss_ring = 1;
-    lds += ring_bytes(a, L->p);
-  }
+  const bool ring = ring_fits(a, L->p, c);
+  if (ring) L->p.loss_ring = 1;
   const bool ar = a.ar.world > 1;
   L->kernel_variant = linear_wave_variant(a, L->p, c, a.mom != nullptr, L->p.stamps != nullptr);
   if (pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant) == nullptr) L->kernel_variant = kWaveGeneric;
@@ -151,6 +160,9 @@ hipError_t linear_wave_prepare(PersistLaunch* L) {
       L->kernel_variant = kWaveGeneric;
     }
   }
+  // The ring is sized here, once the variant is final, from the function the kernel takes its depth
+  // from: the kernel lays out 2 S + depth slots, and a smaller ring would be an LDS overrun.
+  if (ring) lds += ring_bytes(a, L->p, gather_depth(a, c, L->kernel_variant));
   return persist_set_kernel(L, pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant), kThreads, lds);
 }
 

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "sampler.h"
+#include "wave_kernel_rules.h"
 #include "wave_loop_schedule.h"
 #include "wave_row_image.h"
 
@@ -1243,20 +1244,31 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
   if constexpr ((KP & 1) != 0) x[KP - 1] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off + 4 * (KP - 1), 0, 0));
 }
 
-// Whether a lean kernel's step loop has two unrolled group bodies or one (defined next to the
-// instantiation table below).
-constexpr bool lean_two_bodies(int R, int KP, int DOUT, int var, bool ar);
-
 // VAR (WaveKernelVariant, chosen per plan by linear_wave_variant): the generic kernel decides the SGD
 // kind, the loss path, the row masks and the stamps at run time. A lean variant (kWaveLeanPlain /
 // kWaveLeanMom) is the same kernel with the plan's facts as constants -- that SGD kind, the loss ring
 // on, every batch full with B == 16 R rows, no stamps -- so the code a plan never runs is not in the
-// object (one step loop instead of five). Barriers, LDS layout, list handling, prefetch depth and
-// every floating-point operation and its order are the generic kernel's: the results are its bits.
+// object (one step loop instead of five). Barriers, LDS layout, list handling and every floating-point
+// operation and its order are the generic kernel's: the results are its bits.
+//
+// NB, the batches in flight, is the instantiation's (wave_gather_depth, wave_kernel_rules.h): the
+// generic kernels and most lean ones have kWavePrefetch, the two-body lean kernels without all-reduce
+// one more. Everything below follows NB: the register buffers, the prologue's reads and gathers, the
+// steps of an unrolled group, the tail, the loss ring's 2 S + NB slots (the host sizes the LDS from
+// the same function) and the helper waves' reduction bound. What keeps the loop safe holds at every NB:
+//   - the trainer reads list entries for up to NB positions past its last step; each is a valid
+//     dataset row (the next list is zero-filled before the first barrier, lists are padded with 0
+//     up to their stride, a list of an earlier epoch holds that epoch's rows);
+//   - the ring never overwrites an unreduced slot: a read of position P follows step P - NB - 1, so
+//     behind epoch barrier i the helpers reduce positions from (e0 + i - 1) S - NB on while the trainer
+//     writes those before (e0 + i + 1) S - NB (it stops at barrier i + 1), and behind the last epoch
+//     barrier those before (e0 + T + 1) S: 2 S + NB slots at most;
+//   - trainer and helpers take T epoch barriers and the final one for every (S, j0, n), S < NB
+//     included: the schedule takes at most T and the trainer tops them up after the loop.
 //
 // The lean step loop issues the step's math and little else. Its control is wave_loop_schedule.h
-// (host-checked against the generic read_index rule): a launch runs whole kNB-step groups in one
-// unrolled body, then the n % kNB last steps without gathers.
+// (host-checked against the generic read_index rule): a launch runs whole NB-step groups in one
+// unrolled body, then the n % NB last steps without gathers.
 //   unchecked group : all its reads inside the current epoch list, all its slots inside the loss ring:
 //                     no wrap, barrier or ring test; the list entries (lp, lp_y) and the ring slot (rp)
 //                     are running per-lane addresses; one wait per batch, where the step first
@@ -1275,6 +1287,7 @@ template <int R, int KP, int DOUT, int LOSS, bool AR, int VAR = kWaveGeneric>
 __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a, PersistArgs pa) {
   static_assert(R == 1 || R == 2 || R == 4, "rows per lane: 1, 2 or 4");
   constexpr bool LEAN = VAR != kWaveGeneric;
+  constexpr int NB = wave_gather_depth(R, KP, DOUT, VAR, AR);  // batches in flight (register buffers)
   // DOUT == 1: reduce-scatter, one row per lane (rows q & (R-1)); else every lane all rows
   constexpr bool SCATTER = DOUT == 1 && R > 1;
   constexpr int RY = SCATTER ? 1 : R;  // target rows a lane loads / computes the loss of
@@ -1361,7 +1374,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   pstamp(0);
 
   // Only the first epoch's list is on the path to step 0. The next one is
-  // zero-filled (row 0: the trainer reads stale-but-valid indices for the kNB
+  // zero-filled (row 0: the trainer reads stale-but-valid indices for the NB
   // positions past its last step, so every entry it can touch must be a valid
   // dataset row -- no clamp per load) and built by the helper waves after the
   // barrier, while the trainer runs epoch e0.
@@ -1443,7 +1456,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
     }
   };
-  BatchT buf[kNB];
+  BatchT buf[NB];
   const ListCache lc{pa.lcache, pa.ltag, al4(ns_arg)};  // the global cache keeps the unpadded stride
   rank_epoch_indices_or(given_list(pa, e0), list(e0), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples, pa.seed, e0, pa.shuffle,
                      (int)threadIdx.x, kThreads, lc);
@@ -1453,7 +1466,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // Loss ring (pa.loss_ring): the trainer stores each lane's scaled loss share
   // per step (one ds_write), the helper waves add the 64 shares and write
   // losses[] -- the per-step cross-lane loss reduction leaves the critical path.
-  const int ring = (LEAN || loss_ring_arg) ? 2 * S + kNB : 0;  // slots; 2 epochs + prefetch depth never overwrite unread
+  const int ring = (LEAN || loss_ring_arg) ? 2 * S + NB : 0;  // slots; 2 epochs + prefetch depth never overwrite unread
   float* const lring = reinterpret_cast<float*>(elist + 2 * estride + 16);  // after the 8 u64 timer slots
   __syncthreads();
   pstamp(2);
@@ -1502,8 +1515,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         if (i < T)
           rank_epoch_indices_or(given_list(pa, e0 + i + 1), list(e0 + i + 1), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples,
                                 pa.seed, e0 + i + 1, pa.shuffle, ht, hn, lc);
-        // at barrier i the trainer has trained every position before (e0 + i) * S - kNB
-        if (i > 0) reduce_losses(i <= T ? min((int64_t)(e0 + i) * S - kNB, pos0 + n) : pos0 + n);
+        // at barrier i the trainer has trained every position before (e0 + i) * S - NB
+        if (i > 0) reduce_losses(i <= T ? min((int64_t)(e0 + i) * S - NB, pos0 + n) : pos0 + n);
       }
       return;
     }
@@ -1516,8 +1529,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       if (i < T)
         rank_epoch_indices_or(given_list(pa, e0 + i + 1), list(e0 + i + 1), (uint32_t)pa.N, pa.W, pa.rank, pa.num_samples, pa.seed, e0 + i + 1,
                            pa.shuffle, ht, hn, lc);
-      // at barrier i the trainer has trained every position before (e0+i)*S - kNB
-      if (LEAN || ring) reduce_losses(min((int64_t)(e0 + i) * S - kNB, pos0 + n));
+      // at barrier i the trainer has trained every position before (e0+i)*S - NB
+      if (LEAN || ring) reduce_losses(min((int64_t)(e0 + i) * S - NB, pos0 + n));
     }
     if (LEAN || ring) {
       __syncthreads();  // the trainer's final barrier: every step done
@@ -1574,7 +1587,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     load_batch(f, sel_next, sel_y_next, nb_next);
     read_index();
   };
-  // Lean variants: the loop control is wave_loop_schedule.h's (kNB-step groups, unchecked while they
+  // Lean variants: the loop control is wave_loop_schedule.h's (NB-step groups, unchecked while they
   // stay inside one epoch list and the loss ring, checked otherwise). The list entries and the loss
   // ring slot are running per-lane addresses; a checked read / slot resets them at a wrap.
   WaveLoopSchedule sch;
@@ -1582,7 +1595,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   const int* lp_y = elist;   // its own loss row's entry (SCATTER)
   float* rp = lring + lane;  // this lane's share in the next step's ring slot
   if constexpr (LEAN) {
-    sch.init(S, B, estride, e0, j0, n, kNB, ring);
+    sch.init(S, B, estride, e0, j0, n, NB, ring);
     nb_next = B;
   }
   auto read_run = [&]() {
@@ -1711,7 +1724,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
       yimg = y;
     } else if constexpr (LEAN) {
-      // The batch was requested kNB steps ago: one wait for all of it here. Every loaded register
+      // The batch was requested NB steps ago: one wait for all of it here. Every loaded register
       // passes through an empty asm, so the compiler places its wait for the batch's last load in
       // front of the first one and none later (it had one in front of each load's first use).
 #pragma unroll
@@ -1965,30 +1978,30 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     lp_y = lp + rho_own * 16;
     read_run();
 #pragma unroll
-    for (int u = 0; u < kNB; ++u) {
+    for (int u = 0; u < NB; ++u) {
       load_batch(buf[u], sel_next, sel_y_next, B);
       read_checked();
     }
   } else {
     read_index();
 #pragma unroll
-    for (int u = 0; u < kNB; ++u) fetch(buf[u]);
+    for (int u = 0; u < NB; ++u) fetch(buf[u]);
   }
   tk.tick(0);
   int done = 0;
-  const int nfull = n - n % kNB;
+  const int nfull = n - n % NB;
   auto run = [&](auto sgd_tag, auto ring_tag) {
     while (done < nfull && !failed) {
 #pragma unroll
-      for (int u = 0; u < kNB; ++u) {
+      for (int u = 0; u < NB; ++u) {
         train(buf[u], done + u, sgd_tag, ring_tag);
         fetch(buf[u]);
         tk.tick(0);
       }
-      done += kNB;
+      done += NB;
     }
 #pragma unroll
-    for (int u = 0; u < kNB - 1; ++u) {
+    for (int u = 0; u < NB - 1; ++u) {
       if (done < n && !failed) {
         train(buf[u], done, sgd_tag, ring_tag);
         ++done;
@@ -1998,15 +2011,15 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // one loop instantiation per (SGD kind, loss ring): no per-step branch on either. Plain SGD (the
   // reference's SGD(lr)) has its own loop with the ring only; without the ring it takes the
   // weight-decay loop (same values: d = g + 0 * w).
-  // lean: unrolled group bodies (three register buffers in turn). Two of them where the registers
+  // lean: unrolled group bodies (the NB register buffers in turn). Two of them where the registers
   // hold both (lean_two_bodies): a run of unchecked groups is train, gather, read at the running
-  // address, kNB times, under a down-counter and nothing else; a checked group follows every step with a
+  // address, NB times, under a down-counter and nothing else; a checked group follows every step with a
   // checked read and ring slot. Otherwise one body under a uniform per-group flag.
-  // The n % kNB steps after the last group gather nothing.
+  // The n % NB steps after the last group gather nothing.
   auto lean_tail = [&](WaveLoopSchedule& c, int left, auto sgd_tag) {
     int k = 0;
 #pragma unroll
-    for (int u = 0; u < kNB - 1; ++u) {
+    for (int u = 0; u < NB - 1; ++u) {
       if (u < left && !failed) {
         train(buf[u], 0, sgd_tag, std::true_type{});
         if (c.slot_done()) rp = lring + lane;
@@ -2022,7 +2035,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
           sch, n,
           [&]() {
 #pragma unroll
-            for (int u = 0; u < kNB; ++u) {
+            for (int u = 0; u < NB; ++u) {
               train(buf[u], 0, sgd_tag, std::true_type{});
               load_batch(buf[u], sel_next, sel_y_next, B);
               read_run();
@@ -2031,7 +2044,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
           },
           [&](WaveLoopSchedule& c) {
 #pragma unroll
-            for (int u = 0; u < kNB; ++u) {
+            for (int u = 0; u < NB; ++u) {
               train(buf[u], 0, sgd_tag, std::true_type{});
               load_batch(buf[u], sel_next, sel_y_next, B);
               read_checked();
@@ -2045,7 +2058,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
           sch, n,
           [&](WaveLoopSchedule& c, bool checked) {
 #pragma unroll
-            for (int u = 0; u < kNB; ++u) {
+            for (int u = 0; u < NB; ++u) {
               train(buf[u], 0, sgd_tag, std::true_type{});
               load_batch(buf[u], sel_next, sel_y_next, B);
               if (__builtin_expect(checked, 0)) {  // laid out behind the loop: the unchecked path falls through
@@ -2070,7 +2083,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     //   - one wait for the batch and for the list entries read during the previous step;
     //   - the forward products (chunk_dot), then hand_step_2x5 with the next list read issued in
     //     front of it (it has the whole block to land in);
-    //   - behind the block the loss share and the gather of the batch three steps ahead into f, then
+    //   - behind the block the loss share and the gather of the batch NB steps ahead into f, then
     //     the update: five instructions stand between the block and the first VALU instruction that
     //     reads what it wrote (the compiler puts s_nop in front of a VALU instruction that reads a
     //     register an asm statement has just written).
@@ -2168,13 +2181,13 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         sch, n,
         [&]() {
 #pragma unroll
-          for (int u = 0; u < kNB; ++u) train_hand(buf[u]);
+          for (int u = 0; u < NB; ++u) train_hand(buf[u]);
           return true;
         },
         hand_run_end,
         [&](WaveLoopSchedule& c) {
 #pragma unroll
-          for (int u = 0; u < kNB; ++u) {
+          for (int u = 0; u < NB; ++u) {
             train(buf[u], 0, SgdTag{}, std::true_type{});
             load_batch(buf[u], sel_next, sel_y_next, B);
             read_checked();
@@ -2247,18 +2260,6 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the final stores issued above are done
     tl_mark(tl_p, 3);
   }
-}
-
-// Two unrolled group bodies hold the kNB batch buffers (R KP values each, a row record or features
-// and targets) live across both, next to DOUT KP weights (and momenta). Built with two bodies
-// everywhere (tools/wave_kernel_resources.py, profiles/wave_loop_runs.md): every R == 4 kernel ends
-// within a few registers of the 256 or past them (copies through accumulation registers; <4,16,1>
-// gains 88 to 644 bytes of scratch), <2,16,1> and most all-reduce kernels of two outputs or KP >= 8
-// likewise, or they spill already and would carry the spill code twice. Those keep one body under
-// the per-group flag. The rule holds for both lean variants and every loss: `var` does not enter it.
-constexpr bool lean_two_bodies(int R, int KP, int DOUT, int var, bool ar) {
-  (void)var;
-  return ar ? (DOUT == 1 && R <= 2 && KP <= 5) : (R <= 2 && R * KP * DOUT <= 20);
 }
 
 // Instantiation table of one loss and all-reduce flag: (L, R, KP, DOUT)

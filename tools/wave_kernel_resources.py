@@ -5,8 +5,9 @@
     python3 tools/wave_kernel_resources.py DIR              one line per kernel
     python3 tools/wave_kernel_resources.py BASE_DIR DIR     lean kernels of both, and those whose scratch grew
 
-Used to decide which lean configurations keep one group body (lean_two_bodies in
-csrc/kernels/linear_wave_impl.h; profiles/wave_loop_runs.md). Needs no GPU."""
+Used to decide which lean configurations keep one group body and which keep more batches in flight
+(lean_two_bodies, wave_gather_depth in csrc/kernels/wave_kernel_rules.h; profiles/wave_loop_runs.md,
+profiles/wave_gather_depth.md). Needs no GPU."""
 from __future__ import annotations
 
 import glob
