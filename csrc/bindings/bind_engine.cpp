@@ -519,24 +519,28 @@ void bind_engine(py::module_& m) {
   m.def("fused_mlp_lds_bytes", [](int B, int Din, int H, int Dout) { return fused_mlp_lds_bytes(B, Din, H, Dout); });
   // The lean wave loop's control (wave_loop_schedule.h) for a launch of n steps from (e0, j0) over epochs
   // of S batches of B entries: (read offsets, barrier-in-front flags, loss ring slots, barriers taken,
-  // list stride). The kernel runs the same functions.
+  // list stride). The kernel runs the same functions. ring: the loss ring's slots (0: 2 S + depth);
+  // slot0: the slot of the launch's first step (wave_loop_schedule.h: a ring from the list has 3 S slots
+  // and starts a launch at j0 + depth).
   m.def(
       "wave_loop_schedule",
-      [](int S, int B, int e0, int j0, int n, int depth) {
+      [](int S, int B, int e0, int j0, int n, int depth, int ring_arg, int slot0) {
         TORCH_CHECK(S > 0 && B > 0 && j0 >= 0 && j0 < S && n >= 0 && depth > 0, "wave_loop_schedule: bad arguments");
-        const int estride = wave_list_stride(S * B, B), ring = 2 * S + depth;
+        const int estride = wave_list_stride(S * B, B), ring = ring_arg > 0 ? ring_arg : 2 * S + depth;
+        TORCH_CHECK(ring > depth && slot0 >= 0 && slot0 < ring, "wave_loop_schedule: bad ring or start slot");
         std::vector<int> ofs(n + depth + 2), slots(n + 1);
         std::vector<unsigned char> bar(ofs.size());
         int barriers = 0;
         const int nr = wave_loop_enumerate(S, B, estride, e0, j0, n, depth, ring, ofs.data(), bar.data(), (int)ofs.size(),
-                                           slots.data(), (int)slots.size(), &barriers);
+                                           slots.data(), (int)slots.size(), &barriers, slot0);
         TORCH_CHECK(nr >= 0, "wave_loop_schedule: more reads or steps than a launch of n steps has");
         ofs.resize(nr);
         slots.resize(n);
         std::vector<int> flags(bar.begin(), bar.begin() + nr);
         return py::make_tuple(ofs, flags, slots, barriers, estride);
       },
-      py::arg("S"), py::arg("B"), py::arg("e0"), py::arg("j0"), py::arg("n"), py::arg("depth") = kWavePrefetch);
+      py::arg("S"), py::arg("B"), py::arg("e0"), py::arg("j0"), py::arg("n"), py::arg("depth") = kWavePrefetch,
+      py::arg("ring") = 0, py::arg("slot0") = 0);
   // Run length of the lean wave loop from one state (ij reads made in the list, ring slot rslot,
   // groups_left whole groups left in the launch), and the state after advance(run):
   // (run, ij, lofs, rslot), with lofs counted from ij * B.
@@ -558,24 +562,27 @@ void bind_engine(py::module_& m) {
       py::arg("S"), py::arg("B"), py::arg("depth"), py::arg("ring"), py::arg("ij"), py::arg("rslot"),
       py::arg("groups_left"));
   // wave_loop_check_runs over every start j0 of an epoch of S batches and every launch length
-  // 0..n_max, ring = 2 S + depth: (launches, group boundaries checked, first launch that differs as
-  // (j0, n) or None).
+  // 0..n_max: (launches, group boundaries checked, first launch that differs as (j0, n) or None).
+  // ring: the loss ring's slots (0: 2 S + depth); the launch from j0 starts at slot
+  // (slot0 + slot_step j0) % ring (a ring from the list: ring 3 S, slot0 depth, slot_step 1).
   m.def(
       "wave_loop_check_runs",
-      [](int S, int B, int depth, int n_max) {
+      [](int S, int B, int depth, int n_max, int ring_arg, int slot0, int slot_step) {
         TORCH_CHECK(S > 0 && B > 0 && depth > 0 && n_max >= 0, "wave_loop_check_runs: bad arguments");
-        const int estride = wave_list_stride(S * B, B), ring = 2 * S + depth;
+        const int estride = wave_list_stride(S * B, B), ring = ring_arg > 0 ? ring_arg : 2 * S + depth;
+        TORCH_CHECK(ring > depth && slot0 >= 0 && slot_step >= 0, "wave_loop_check_runs: bad ring or start slot");
         int64_t launches = 0, boundaries = 0;
         for (int j0 = 0; j0 < S; ++j0)
           for (int n = 0; n <= n_max; ++n) {
-            const long c = wave_loop_check_runs(S, B, estride, j0 & 1, j0, n, depth, ring);
+            const long c = wave_loop_check_runs(S, B, estride, j0 & 1, j0, n, depth, ring, (slot0 + slot_step * j0) % ring);
             if (c < 0) return py::make_tuple(launches, boundaries, py::cast(std::make_pair(j0, n)));
             ++launches;
             boundaries += c;
           }
         return py::make_tuple(launches, boundaries, py::object(py::none()));
       },
-      py::arg("S"), py::arg("B"), py::arg("depth"), py::arg("n_max"));
+      py::arg("S"), py::arg("B"), py::arg("depth"), py::arg("n_max"), py::arg("ring") = 0, py::arg("slot0") = 0,
+      py::arg("slot_step") = 0);
 
   // Row image of the wave engine (wave_row_image.h). wave_row_image_layout(Din, KP): (floats per
   // record RS, bytes per row, slot of 1.0f or -1, slot of y, source[q][s] of every record slot: a

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "wave_kernel_rules.h"
+#include "wave_loop_schedule.h"
 #include "wave_row_image.h"
 
 namespace ptdt {
@@ -21,6 +22,7 @@ size_t lds_bytes(const FusedMlpArgs& a, const PersistArgs& p) {  // two epoch in
   return (size_t)2 * wave_list_stride(p.num_samples, a.B) * sizeof(int) + 8 * sizeof(unsigned long long);
 }
 constexpr size_t kStaticLds = 512;  // layout F's static pair-exchange scratch (linear_wave_impl.h)
+static_assert(kStaticLds == kWaveStaticLdsBytes && 160 * 1024 == kWaveLdsBytes, "wave_ring_from_list budgets the same LDS");
 // loss ring of layout F: (2 epochs + the kernel's batches in flight) steps x 64 lane shares
 size_t ring_bytes(const FusedMlpArgs& a, const PersistArgs& p, int depth = kWavePrefetch) {
   const int S = (p.num_samples + a.B - 1) / a.B;
@@ -160,9 +162,15 @@ hipError_t linear_wave_prepare(PersistLaunch* L) {
       L->kernel_variant = kWaveGeneric;
     }
   }
-  // The ring is sized here, once the variant is final, from the function the kernel takes its depth
-  // from: the kernel lays out 2 S + depth slots, and a smaller ring would be an LDS overrun.
-  if (ring) lds += ring_bytes(a, L->p, gather_depth(a, c, L->kernel_variant));
+  // The ring is sized here, once the variant is final, from the functions the kernel takes its depth
+  // and its slots from (a smaller ring would be an LDS overrun): 2 S + depth slots, or 3 S counted from
+  // the list in a lean kernel without the all-reduce where they fit (wave_loop_schedule.h).
+  if (ring) {
+    const int depth = gather_depth(a, c, L->kernel_variant), S = (L->p.num_samples + a.B - 1) / a.B;
+    const bool from_list = L->kernel_variant != kWaveGeneric && !ar &&
+                           wave_ring_from_list(S, depth, wave_list_stride(L->p.num_samples, a.B));
+    lds += (size_t)wave_ring_slots(S, depth, from_list) * kWaveRingSlotBytes;
+  }
   return persist_set_kernel(L, pick(a.loss_kind, ar, c.L, c.R, c.kp, a.Dout, L->kernel_variant), kThreads, lds);
 }
 

@@ -1254,15 +1254,18 @@ __device__ __forceinline__ void buffer_load_chunk(__amdgpu_buffer_rsrc_t r, uint
 // NB, the batches in flight, is the instantiation's (wave_gather_depth, wave_kernel_rules.h): the
 // generic kernels and most lean ones have kWavePrefetch, the two-body lean kernels without all-reduce
 // one more. Everything below follows NB: the register buffers, the prologue's reads and gathers, the
-// steps of an unrolled group, the tail, the loss ring's 2 S + NB slots (the host sizes the LDS from
-// the same function) and the helper waves' reduction bound. What keeps the loop safe holds at every NB:
+// steps of an unrolled group, the tail, the loss ring's slots (2 S + NB, or 3 S; the host sizes the LDS
+// from the same functions) and the helper waves' reduction bound. What keeps the loop safe holds at every NB:
 //   - the trainer reads list entries for up to NB positions past its last step; each is a valid
 //     dataset row (the next list is zero-filled before the first barrier, lists are padded with 0
 //     up to their stride, a list of an earlier epoch holds that epoch's rows);
 //   - the ring never overwrites an unreduced slot: a read of position P follows step P - NB - 1, so
 //     behind epoch barrier i the helpers reduce positions from (e0 + i - 1) S - NB on while the trainer
 //     writes those before (e0 + i + 1) S - NB (it stops at barrier i + 1), and behind the last epoch
-//     barrier those before (e0 + T + 1) S: 2 S + NB slots at most;
+//     barrier those before (e0 + T + 1) S: 2 S + NB slots at most. The lean kernels without the
+//     all-reduce take 3 S slots counted from the list where NB <= S and the LDS holds them, so that the
+//     ring ends only where the list switches (wave_ring_from_list in wave_loop_schedule.h, with the
+//     argument; tests/test_wave_ring_origin.py);
 //   - trainer and helpers take T epoch barriers and the final one for every (S, j0, n), S < NB
 //     included: the schedule takes at most T and the trainer tops them up after the loop.
 //
@@ -1298,9 +1301,9 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   constexpr bool IMG = LEAN && DOUT == 1 && LOSS != kLossCEIndex;
   constexpr bool PKT = IMG && (KP & 1) != 0;  // packed backward tail {x[KP-1], 1} . {g, g}
   using BatchT = Batch<R, KP, DOUT, RY, IMG>;
-  // The hand-placed step (train_hand, hand_step_2x5): the unchecked group body of the two-body image
+  // The hand-placed step (train_hand, hand_step_2x5): both group bodies of the two-body image
   // kernels of Linear(17..20, 1) at B = 32 without the in-kernel all-reduce. Every other body and every
-  // other kernel keeps the compiler's step (train). The lean-plain ones add the column sums as a
+  // other kernel, and the tail, keeps the compiler's step (train). The lean-plain ones add the column sums as a
   // reduce-scatter and update from its lanes (hand_step_2x5_rs, hand_sgd_bcast; profiles/wave_colsum_scatter.md).
   constexpr bool kHandStep = IMG && SCATTER && R == 2 && KP == 5 && !AR && lean_two_bodies(R, KP, DOUT, VAR, AR);
   extern __shared__ int elist[];
@@ -1466,7 +1469,20 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   // Loss ring (pa.loss_ring): the trainer stores each lane's scaled loss share
   // per step (one ds_write), the helper waves add the 64 shares and write
   // losses[] -- the per-step cross-lane loss reduction leaves the critical path.
-  const int ring = (LEAN || loss_ring_arg) ? 2 * S + NB : 0;  // slots; 2 epochs + prefetch depth never overwrite unread
+  // Slots: 2 epochs + prefetch depth never overwrite unread. The lean kernels without the all-reduce
+  // count the slots from the list where 3 S slots fit (wave_loop_schedule.h): the ring then ends only
+  // where the list switches, and the launch's first step has slot j0 + NB.
+  // Every other kernel keeps its expressions as they were (kListRing false): its code is unchanged.
+  constexpr bool kListRing = LEAN && !AR;
+  int ring_slots, ring_first = 0;
+  if constexpr (kListRing) {
+    const bool from_list = wave_ring_from_list(S, NB, estride);
+    ring_slots = wave_ring_slots(S, NB, from_list);
+    ring_first = wave_ring_first_slot(j0, NB, from_list);
+  } else {
+    ring_slots = (LEAN || loss_ring_arg) ? 2 * S + NB : 0;
+  }
+  const int ring = ring_slots, slot0 = ring_first;
   float* const lring = reinterpret_cast<float*>(elist + 2 * estride + 16);  // after the 8 u64 timer slots
   __syncthreads();
   pstamp(2);
@@ -1483,7 +1499,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     auto reduce_losses = [&](int64_t hi) {
       const int grp = ht >> 4, sub = ht & 15, ngrp = hn >> 4;
       for (int64_t P = lo + grp; P < hi; P += ngrp) {
-        const float* sh = lring + ((int)(P - pos0) % ring) * 64;
+        const float* sh = lring + (kListRing ? (int)(P - pos0 + slot0) % ring : (int)(P - pos0) % ring) * 64;
         float4 v = *reinterpret_cast<const float4*>(sh + 4 * sub);
         if constexpr (LEAN && LOSS != kLossCEIndex) {
           // the lean trainer stores each lane's loss unmasked and unscaled: the owner select (a batch
@@ -1593,8 +1609,11 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   WaveLoopSchedule sch;
   const int* lp = elist;     // this lane's entries of the next read (rows rho * 16 + i)
   const int* lp_y = elist;   // its own loss row's entry (SCATTER)
-  float* rp = lring + lane;  // this lane's share in the next step's ring slot
-  if constexpr (LEAN) {
+  float* rp = kListRing ? lring + slot0 * 64 + lane : lring + lane;  // this lane's share in the next step's ring slot
+  if constexpr (kListRing) {
+    sch.init(S, B, estride, e0, j0, n, NB, ring, slot0);
+    nb_next = B;
+  } else if constexpr (LEAN) {
     sch.init(S, B, estride, e0, j0, n, NB, ring);
     nb_next = B;
   }
@@ -2078,8 +2097,10 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
   using NoMom = std::integral_constant<int, kSgdNoMom>;
   using Mom = std::integral_constant<int, kSgdMom>;
   if constexpr (kHandStep) {
-    // The unchecked group body with the step placed by hand; the checked body and the tail are
-    // run_lean's. One step, for batch f (the floating-point operations of train, in its order):
+    // Both group bodies with the step placed by hand; the tail is run_lean's. A checked group's step
+    // leaves the list read out: the checked read (barrier, list switch, address reset) and the checked
+    // ring slot follow the step, where the barrier has the step's loss share in front of it. One
+    // step, for batch f (the floating-point operations of train, in its order):
     //   - one wait for the batch and for the list entries read during the previous step;
     //   - the forward products (chunk_dot), then hand_step_2x5 with the next list read issued in
     //     front of it (it has the whole block to land in);
@@ -2097,7 +2118,8 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
     // -lr, -lr_b as registers for the update that reads them
     float hgx = 0.f, hgy = 0.f, nlr = -lr, nlr_b = -lr_b;
     if constexpr (VAR == kWaveLeanPlain) asm volatile("" : "+v"(nlr), "+v"(nlr_b));
-    auto train_hand = [&](BatchT& f) {
+    // checked_tag: a step of a checked group makes no read of its own; the caller's checked read follows it.
+    auto train_hand = [&](BatchT& f, auto checked_tag) {
       // the pin only reads (see above); the scheduling barrier keeps every use of the batch behind the wait
       asm volatile("" ::"v"(f.img[1][1]), "v"(f.img[1][0]), "v"(f.img[0][1]), "v"(f.img[0][0]), "v"(sel_next[0]), "v"(sel_next[1]));
       __builtin_amdgcn_sched_barrier(0);
@@ -2111,7 +2133,7 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
       }
       const float zp0 = chunk_dot<KP>(x[0], W[0]), zp1 = chunk_dot<KP>(x[1], W[0]);
       uint32_t o0 = (uint32_t)sel_next[0], o1 = (uint32_t)sel_next[1];
-      read_run();
+      if constexpr (!decltype(checked_tag)::value) read_run();
       __builtin_amdgcn_sched_barrier(0);
       f2v hs[3];
       float lraw;
@@ -2164,9 +2186,9 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         Gbk[0] = gr[KP];
       }
     };
-    // Where a run of unchecked groups ends: the last step's gradient from the two registers of its
-    // scattered sums, once (the momentum kernels copied it per step above). A checked group or the tail
-    // behind the run overwrites it as they overwrite every step's.
+    // Where a run of unchecked groups or a checked group ends: the last step's gradient from the two registers of its
+    // scattered sums, once (the momentum kernels copied it per step above). The tail behind it overwrites
+    // it as it overwrites every step's.
     auto hand_run_end = [&]() {
       if constexpr (VAR == kWaveLeanPlain) {
         Gk[0][0] = dpp_f<0x150 + kHsBcast[0]>(hgx);
@@ -2181,18 +2203,18 @@ __global__ void __launch_bounds__(kThreads) linear_wave_f_kernel(FusedMlpArgs a,
         sch, n,
         [&]() {
 #pragma unroll
-          for (int u = 0; u < NB; ++u) train_hand(buf[u]);
+          for (int u = 0; u < NB; ++u) train_hand(buf[u], std::false_type{});
           return true;
         },
         hand_run_end,
         [&](WaveLoopSchedule& c) {
 #pragma unroll
           for (int u = 0; u < NB; ++u) {
-            train(buf[u], 0, SgdTag{}, std::true_type{});
-            load_batch(buf[u], sel_next, sel_y_next, B);
+            train_hand(buf[u], std::true_type{});
             read_checked();
             if (c.slot_done()) rp = lring + lane;
           }
+          hand_run_end();
           return true;
         },
         [&](WaveLoopSchedule& c, int left) { return lean_tail(c, left, SgdTag{}); });

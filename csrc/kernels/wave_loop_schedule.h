@@ -27,6 +27,34 @@
 
 namespace ptdt {
 
+// The loss ring of a lean launch (linear_wave_impl.h; the host sizes the LDS from the same functions).
+// Position P = e0 S + j0 + k (step k of the launch) stores its loss shares in one slot; the helper waves
+// reduce the slots behind the epoch barriers.
+//   from the launch start : slot k % (2 S + depth). The ring ends wherever the launch's start put it, and
+//                           the group that holds the end is a checked one for that alone.
+//   from the list         : slot (j0 + k + depth) % (3 S). The read behind step k is position
+//                           P + depth + 1, so the list switches behind the step with j0 + k + depth + 1 a
+//                           multiple of S, and the ring ends behind a step with j0 + k + depth + 1 a
+//                           multiple of 3 S: every ring end is a list switch, which a checked group holds
+//                           already, and run()'s ring bound never ends a run ((ring - rslot - 1) >=
+//                           S - ij between groups, as rslot % S == ij - 1 there).
+// Both are safe for the same reason: behind barrier i the helpers reduce positions from
+// (e0 + i - 1) S - depth on while the trainer writes those before (e0 + i + 1) S - depth, or before
+// (e0 + i + 1) S behind the launch's last barrier: 2 S + depth consecutive positions at most are live,
+// and consecutive positions have different slots while they are no more than the ring. 3 S holds them
+// iff depth <= S. The ring from the list is taken where that holds and the LDS has room for it
+// (wave_ring_from_list); every other launch keeps the ring from the launch start.
+constexpr int kWaveLdsBytes = 160 * 1024;        // LDS of one workgroup
+constexpr int kWaveRingSlotBytes = 64 * 4;       // one float per lane of the trainer wave
+constexpr int kWaveStaticLdsBytes = 512;         // layout F's static pair-exchange scratch
+// dynamic LDS of a layout-F launch in front of the ring: two epoch lists of estride entries, 8 timer slots
+PTDT_HD inline long wave_lists_bytes(int estride) { return 2L * estride * 4 + 8 * 8; }
+PTDT_HD inline bool wave_ring_from_list(int S, int depth, int estride) {
+  return S >= depth && wave_lists_bytes(estride) + 3L * S * kWaveRingSlotBytes + kWaveStaticLdsBytes <= kWaveLdsBytes;
+}
+PTDT_HD inline int wave_ring_slots(int S, int depth, bool from_list) { return from_list ? 3 * S : 2 * S + depth; }
+PTDT_HD inline int wave_ring_first_slot(int j0, int depth, bool from_list) { return from_list ? j0 + depth : 0; }
+
 struct WaveLoopSchedule {
   int S;         // steps (batches) per epoch
   int B;         // list entries per batch
@@ -40,7 +68,8 @@ struct WaveLoopSchedule {
   int barriers;  // barriers taken
   int rslot;     // loss ring slot of the next step (< ring between steps)
 
-  PTDT_HD void init(int S_, int B_, int estride_, int e0, int j0, int n, int depth_, int ring_) {
+  // slot0: the ring slot of the launch's first step (wave_ring_first_slot)
+  PTDT_HD void init(int S_, int B_, int estride_, int e0, int j0, int n, int depth_, int ring_, int slot0 = 0) {
     S = S_;
     B = B_;
     estride = estride_;
@@ -51,7 +80,7 @@ struct WaveLoopSchedule {
     par = e0 & 1;
     lofs = par * estride_ + j0 * B_;
     barriers = 0;
-    rslot = 0;
+    rslot = slot0;
   }
   // The launch's first read, at the start position itself (j0 < S): no list switch, no barrier.
   PTDT_HD int first() {
@@ -183,11 +212,12 @@ PTDT_HD inline int wave_loop_run_flagged(WaveLoopSchedule& s, int n, Group&& gro
 // state behind the running addresses shows in what is returned. Returns the number of reads, or -1
 // if a capacity is too small.
 inline int wave_loop_enumerate(int S, int B, int estride, int e0, int j0, int n, int depth, int ring, int* ofs,
-                               unsigned char* bar, int cap_reads, int* slots, int cap_slots, int* barriers_out) {
+                               unsigned char* bar, int cap_reads, int* slots, int cap_slots, int* barriers_out,
+                               int slot0 = 0) {
   WaveLoopSchedule s;
-  s.init(S, B, estride, e0, j0, n, depth, ring);
+  s.init(S, B, estride, e0, j0, n, depth, ring, slot0);
   int nr = 0, nsl = 0;
-  int lp = 0, rp = 0;  // running entry offset of the next read, running ring slot of the next step
+  int lp = 0, rp = slot0;  // running entry offset of the next read, running ring slot of the next step
   auto read = [&](bool b) {
     if (nr < cap_reads) {
       ofs[nr] = lp;
@@ -243,9 +273,9 @@ inline int wave_loop_enumerate(int S, int B, int estride, int e0, int j0, int n,
 // every group run(groups left) must be the number of times fits() / advance() can be repeated from
 // there, and advance(that many) must leave the state those repeats leave. Returns the number of
 // group boundaries checked, or -1 - (index of the first one that differs).
-inline long wave_loop_check_runs(int S, int B, int estride, int e0, int j0, int n, int depth, int ring) {
+inline long wave_loop_check_runs(int S, int B, int estride, int e0, int j0, int n, int depth, int ring, int slot0 = 0) {
   WaveLoopSchedule s;
-  s.init(S, B, estride, e0, j0, n, depth, ring);
+  s.init(S, B, estride, e0, j0, n, depth, ring, slot0);
   bool b, sw;
   s.first();
   for (int u = 0; u < depth; ++u) s.next(&b, &sw);
